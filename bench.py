@@ -9,7 +9,7 @@ committed, so every step does identical work on data already resident in HBM.
   N = 1   workload = BAL Ladybug-1723 shape (1 723 cameras / 156 502 points / 678 718 observations,
           seeded synthetic: 70 % ring-local + 30 % half-lap revisit co-visibility); ordering: see `--ordering`
           (BASELINE config 3: "LM + METIS ordering" — `--ordering metis` feeds the reference's own METIS result).
-          The line also carries `secondary`: pose3_100k ms/step on this one GPU — the N=1 anchor of the N>1 curve.
+          With `--full` the line also carries `secondary`: pose3_100k ms/step on this one GPU — the N=1 anchor of the N>1 curve.
   N > 1   `python bench.py --gpus N` starts its own N ranks (torch.distributed.run) when it was not started
           under torchrun.  One process per GPU (torch.distributed, backend nccl = RCCL over xGMI): the ranks solve ONE
           100 000-pose Pose3 graph together ("100k-pose g2o @1/2/4/8", BASELINE's metric) — gsx_set_shard:
@@ -20,7 +20,10 @@ committed, so every step does identical work on data already resident in HBM.
           strong scaling on real xGMI and the RCCL branch of the exchange are unmeasured until the driver's
           multi-GPU run.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`ms_per_step`, ...).  `--full` adds what takes runs of its own after the timed steps: phase and per-kernel timing passes
+(`ms_per_linear_solve`, `phases_ms`, `kernels`, `roofline`), the CPU baseline, the N=1 anchor (`secondary`) and, for N > 1,
+the sharded-vs-single-GPU check.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -56,7 +59,7 @@ def parse():
                     help="only the launch plumbing: rendezvous, barrier, MAX over ranks, rank 0's line — no GPU work "
                          "(tests/test_distributed_gloo.py runs `bench.py --gpus 2 --backend gloo --launch-check` on CPU)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N=1: skip the pose-graph anchor (pose3_100k ms/step, the N=1 point of the sharded curve) that is "
+                    help="N=1 with --full: skip the pose-graph anchor (pose3_100k ms/step, the N=1 point of the sharded curve) that is "
                          "measured after the headline workload's timed region")
     ap.add_argument("--lam", type=float, default=1e-5)
     ap.add_argument("--hard-prior", action="store_true",
@@ -65,7 +68,7 @@ def parse():
     ap.add_argument("--amalgamation", default=None, metavar="RELAX,MAXF",
                     help="relaxed clique amalgamation (gsx_set_amalgamation); default: the library's own choice "
                          "(GSX_AMALGAMATION_AUTO, what a drop-in caller gets), 0,128 = the reference's cliques")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="host threads of the CPU baseline (a one-GPU box's share of the host is 16 cores)")
@@ -85,7 +88,42 @@ def parse():
                     help="N>1 with --replicas: after the timed replicas, rank 0 also starts a separate N-rank sharded run "
                          "of this workload (own processes, hard time limit) and attaches its result under \"shard_run\"")
     ap.add_argument("--shard-extra-timeout", type=float, default=240.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the phase and per-kernel timing "
+                         "passes (phases_ms, kernels, roofline, ms_per_linear_solve), the CPU baseline, the N=1 pose-graph "
+                         "anchor and the sharded-vs-single-GPU check; without it a run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64): trial_errors = (linear "
+                         "error at 0, at delta, nonlinear error of the trial point) and trial_values = the packed trial "
+                         "point (values retracted by the step's delta)")
     return ap.parse_args()
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def trial_outputs(be):
+    """The trial point of the last lm_trial, read back without disturbing the handle: commit it, read the values, put the
+    old values back (the next lm_trial relinearizes at them, as before).  Collective on a sharded handle."""
+    v0 = be.get_values()
+    be.retract(None, commit=True, want_error=False)
+    trial = be.get_values()
+    be.set_values(v0)
+    return trial
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> float64 array; a fixed seeded sample of each array if the whole set exceeds DUMP_BYTES_MAX."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if total > DUMP_BYTES_MAX:
+            keep = max(1, int(a.size * DUMP_BYTES_MAX / total) - 1)
+            if keep < a.size:
+                a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def make_problem(name, seed):
@@ -230,7 +268,7 @@ def run_shard_child(world, workload, backend, timeout_s):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--workload", workload, "--steps", "20", "--warmup", "3",
-           "--no-cpu-baseline", "--backend", backend]
+           "--no-cpu-baseline", "--backend", backend, "--full"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "GROUP_RANK", "ROLE_RANK",
                         "LOCAL_WORLD_SIZE", "ROLE_WORLD_SIZE", "TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT",
@@ -421,7 +459,7 @@ def main():
         # one LM inner iteration without the policy: linearize, H assembly, damped factorization, back-substitution,
         # both linearized errors, retract, nonlinear error of the trial point — one host synchronisation, as in
         # gsx_lm_optimize
-        be.lm_trial(True, lam, False)
+        return be.lm_trial(True, lam, False)
 
     def barrier():
         if dist is not None:
@@ -430,7 +468,7 @@ def main():
         be.synchronize()
 
     shard_check = None
-    if sharded and world > 1:
+    if args.full and sharded and world > 1:
         # the sharded trial against the plain single-GPU one on the same inputs (rank 0 runs the reference handle)
         e_sh = be.lm_trial(True, lam, False)
         if rank == 0:
@@ -454,73 +492,80 @@ def main():
     barrier()
     for k in exchange:
         exchange[k] = 0
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     elapsed = time.perf_counter() - t0
     value, ms_step = D.aggregate_throughput(dist, args.steps, elapsed, device=red_dev)
     if sharded and world > 1:
         value /= world   # ONE job: its iterations per second, not the sum over replicas
     exchange_timed = dict(exchange)
-    # phase times (HIP events around the phases) from a pass of their own, after the timed region
-    be.set_profiling(0)
-    be.reset_stats()
-    for _ in range(min(args.steps, 10)):
-        step()
+    if args.dump_outputs is not None:   # (after the timed region: what a caller of the last step receives)
+        outputs = {"trial_errors": np.array(last, dtype=np.float64), "trial_values": trial_outputs(be)}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     st = be.stats()
-    ms_solve = (st["ms_factorize"] + st["ms_backsolve"]) / max(st["n_factorize"], 1)
+    if args.full:
+        # phase times (HIP events around the phases) from a pass of their own, after the timed region
+        be.set_profiling(0)
+        be.reset_stats()
+        for _ in range(min(args.steps, 10)):
+            step()
+        st = be.stats()
+        ms_solve = (st["ms_factorize"] + st["ms_backsolve"]) / max(st["n_factorize"], 1)
 
-    # ---- per-kernel timing pass (HIP events on the library's stream around every launch) ------------
-    be.set_profiling(1)
-    be.reset_stats()
-    for _ in range(3):
-        step()
-    st_prof = be.stats()
-    if sharded:   # this rank's share: its own subtrees + the cap (which every rank factors, in the blocked class)
-        _, f_owner, _ = be.shard_info()
-        split = front_split(be, arrays, mine=(f_owner == shard_rank) | (f_owner < 0))
-    else:
-        split = front_split(be, arrays)
-    nfac = max(st_prof["n_factorize"], 1)
-    phases = {k: st_prof[k] / nfac for k in ("ms_linearize", "ms_assemble_hessian", "ms_factorize", "ms_backsolve",
-                                             "ms_linear_error", "ms_retract", "ms_error")}
-    # every kernel of the path: (HIP-event name, rocprof kernel name, bound, algorithmic amount per
-    # factorization — bytes for "hbm", flops for "mfma")
-    kernels = [
-        ("factor_leaf", "front_leaf_kernel", "hbm", split["leaf_bytes"]),
-        ("factor_small", "front_small_kernel (+front_tree, front_medium)", "hbm", split["small_bytes"]),
-        ("big_diag", "big_diag_kernel", "mfma", split["big_potrf_flops"]),
-        ("big_rows", "big_rows_kernel", "mfma", split["big_trsm_flops"]),
-        ("big_schur", "big_schur_kernel", "mfma", split["big_syrk_flops"]),
-        ("big_gather", "big_gather_seg_kernel(+combine)", "hbm", split["gather_bytes"]),
-        ("assemble_hessian", "assemble_h_kernel(+hessian_diag)", "hbm", st["jacobian_bytes"] + st["hessian_bytes"]),
-        ("backsolve", "backsolve_kernel (all levels)", "hbm", split["lpanel_bytes"]),
-    ]
-    per_kernel = {}
-    for ev, kname, bound, amount in kernels:
-        avg_ms, n = be.kernel_time(ev)
-        tot = avg_ms * n / nfac
-        per_kernel[kname] = dict(ms_per_factorization=tot, launches_per_factorization=n / nfac, avg_launch_ms=avg_ms,
-                                 bound=bound, algorithmic_per_factorization=amount)
-    be.set_profiling(0)
-    dom = max(per_kernel, key=lambda k: per_kernel[k]["ms_per_factorization"])
-    dk = per_kernel[dom]
-    per_launch = dk["algorithmic_per_factorization"] / max(dk["launches_per_factorization"], 1e-9)
-    if dk["bound"] == "hbm":
-        achieved = per_launch / (dk["avg_launch_ms"] * 1e-3) / 1e9 if dk["avg_launch_ms"] > 0 else 0.0
-        peak, unit = HBM_PEAK_GBS, "GB/s"
-    else:
-        achieved = per_launch / (dk["avg_launch_ms"] * 1e-3) / 1e12 if dk["avg_launch_ms"] > 0 else 0.0
-        peak, unit = FP64_PEAK_TFLOPS, "TFLOP/s"
-    traffic, traffic_src = pmc_traffic(dom, args.workload)
-    roofline = dict(kernel=dom, bound=dk["bound"], achieved=achieved, peak=peak, unit=unit, frac=achieved / peak,
-                    traffic=traffic, traffic_source=traffic_src,
-                    launches_per_factorization=dk["launches_per_factorization"],
-                    avg_launch_ms=dk["avg_launch_ms"], algorithmic_per_launch=per_launch)
-    tot_leaf = per_kernel["front_leaf_kernel"]["ms_per_factorization"]
-    tot_small = per_kernel["front_small_kernel (+front_tree, front_medium)"]["ms_per_factorization"]
-    tot_big = sum(per_kernel[k]["ms_per_factorization"] for k in per_kernel if k.startswith("big_"))
+        # ---- per-kernel timing pass (HIP events on the library's stream around every launch) ------------
+        be.set_profiling(1)
+        be.reset_stats()
+        for _ in range(3):
+            step()
+        st_prof = be.stats()
+        if sharded:   # this rank's share: its own subtrees + the cap (which every rank factors, in the blocked class)
+            _, f_owner, _ = be.shard_info()
+            split = front_split(be, arrays, mine=(f_owner == shard_rank) | (f_owner < 0))
+        else:
+            split = front_split(be, arrays)
+        nfac = max(st_prof["n_factorize"], 1)
+        phases = {k: st_prof[k] / nfac for k in ("ms_linearize", "ms_assemble_hessian", "ms_factorize", "ms_backsolve",
+                                                 "ms_linear_error", "ms_retract", "ms_error")}
+        # every kernel of the path: (HIP-event name, rocprof kernel name, bound, algorithmic amount per
+        # factorization — bytes for "hbm", flops for "mfma")
+        kernels = [
+            ("factor_leaf", "front_leaf_kernel", "hbm", split["leaf_bytes"]),
+            ("factor_small", "front_small_kernel (+front_tree, front_medium)", "hbm", split["small_bytes"]),
+            ("big_diag", "big_diag_kernel", "mfma", split["big_potrf_flops"]),
+            ("big_rows", "big_rows_kernel", "mfma", split["big_trsm_flops"]),
+            ("big_schur", "big_schur_kernel", "mfma", split["big_syrk_flops"]),
+            ("big_gather", "big_gather_seg_kernel(+combine)", "hbm", split["gather_bytes"]),
+            ("assemble_hessian", "assemble_h_kernel(+hessian_diag)", "hbm", st["jacobian_bytes"] + st["hessian_bytes"]),
+            ("backsolve", "backsolve_kernel (all levels)", "hbm", split["lpanel_bytes"]),
+        ]
+        per_kernel = {}
+        for ev, kname, bound, amount in kernels:
+            avg_ms, n = be.kernel_time(ev)
+            tot = avg_ms * n / nfac
+            per_kernel[kname] = dict(ms_per_factorization=tot, launches_per_factorization=n / nfac, avg_launch_ms=avg_ms,
+                                     bound=bound, algorithmic_per_factorization=amount)
+        be.set_profiling(0)
+        dom = max(per_kernel, key=lambda k: per_kernel[k]["ms_per_factorization"])
+        dk = per_kernel[dom]
+        per_launch = dk["algorithmic_per_factorization"] / max(dk["launches_per_factorization"], 1e-9)
+        if dk["bound"] == "hbm":
+            achieved = per_launch / (dk["avg_launch_ms"] * 1e-3) / 1e9 if dk["avg_launch_ms"] > 0 else 0.0
+            peak, unit = HBM_PEAK_GBS, "GB/s"
+        else:
+            achieved = per_launch / (dk["avg_launch_ms"] * 1e-3) / 1e12 if dk["avg_launch_ms"] > 0 else 0.0
+            peak, unit = FP64_PEAK_TFLOPS, "TFLOP/s"
+        traffic, traffic_src = pmc_traffic(dom, args.workload)
+        roofline = dict(kernel=dom, bound=dk["bound"], achieved=achieved, peak=peak, unit=unit, frac=achieved / peak,
+                        traffic=traffic, traffic_source=traffic_src,
+                        launches_per_factorization=dk["launches_per_factorization"],
+                        avg_launch_ms=dk["avg_launch_ms"], algorithmic_per_launch=per_launch)
+        tot_leaf = per_kernel["front_leaf_kernel"]["ms_per_factorization"]
+        tot_small = per_kernel["front_small_kernel (+front_tree, front_medium)"]["ms_per_factorization"]
+        tot_big = sum(per_kernel[k]["ms_per_factorization"] for k in per_kernel if k.startswith("big_"))
 
     out = {
         "metric": "lm_iterations_per_sec", "value": value, "unit": "LM iterations/s", "n_gpus": world,
@@ -534,15 +579,15 @@ def main():
                    "replicas": 1 if sharded else world,
                    "parallelism": (f"shard{world}" if world > 1 else f"rank 0 of shard{args.shard_share}, exchange "
                                    "stubbed") if sharded else f"replicas{world}"},
-        "ms_per_linear_solve": ms_solve,
-        "phases_ms": phases,
-        "factor_leaf_ms": tot_leaf, "factor_small_ms": tot_small, "factor_big_ms": tot_big,
         "symbolic": {k: st[k] for k in ("n_fronts", "n_levels", "max_front_dim", "max_front_rows", "n_small_fronts",
                                         "n_big_fronts", "n_medium_fronts", "n_tree_fronts", "n_upper_levels", "factor_flops", "front_bytes", "lpanel_bytes",
                                         "jacobian_bytes", "hessian_bytes", "total_dim")},
-        "front_split": split, "kernels": per_kernel, "host_ordering_s": t_order, "host_symbolic_s": t_symbolic,
-        "roofline": roofline,
+        "host_ordering_s": t_order, "host_symbolic_s": t_symbolic,
     }
+    if args.full:
+        out.update({"ms_per_linear_solve": ms_solve, "phases_ms": phases,
+                    "factor_leaf_ms": tot_leaf, "factor_small_ms": tot_small, "factor_big_ms": tot_big,
+                    "front_split": split, "kernels": per_kernel, "roofline": roofline})
     if sharded:
         info, owner, _ = be.shard_info()
         out["shard"] = dict(info, exchange_path=exchange_path, trial_vs_single_gpu_max_rel_diff=shard_check[0] if shard_check else None,
@@ -552,17 +597,18 @@ def main():
                             fronts_per_rank=[int((owner == r).sum()) for r in range(info["world"])])
         # roofline / kernels / front_split above are RANK 0's: its launches against the algorithmic amounts of the
         # fronts it processes (own subtrees + cap)
-        out["roofline"]["of"] = f"rank {shard_rank} of {shard_world}: own subtree fronts + cap fronts"
+        if args.full:
+            out["roofline"]["of"] = f"rank {shard_rank} of {shard_world}: own subtree fronts + cap fronts"
     out["config"]["shape"] = {k: (v if not hasattr(v, "tolist") else None) for k, v in arrays.meta.items()
                               if not hasattr(v, "shape")}
 
     # ---- CPU baseline (rank 0; the other ranks of a sharded job wait at the barrier below) ---------
-    if rank == 0 and not args.no_cpu_baseline and args.shard_share <= 1 and (world == 1 or sharded):
+    if args.full and rank == 0 and not args.no_cpu_baseline and args.shard_share <= 1 and (world == 1 or sharded):
         out["cpu_baseline"] = cpu_baseline(arrays, ordering, lam, args.workload, args.cpu_threads, args.cpu_iters)
         out["speedup_vs_cpu_port_threads"] = value / out["cpu_baseline"]["value"]
         out["speedup_vs_cpu_port_1_thread"] = value / out["cpu_baseline"]["single_thread"]["value"]
     # ---- N=1: the pose-graph anchor (the N=1 point of the curve `--gpus N` measures on pose3_100k) ---------
-    if rank == 0 and world == 1 and not sharded and not args.no_secondary and args.workload == "bal1723":
+    if args.full and rank == 0 and world == 1 and not sharded and not args.no_secondary and args.workload == "bal1723":
         be.close()
         try:
             out["secondary"] = [anchor_ms_per_step("pose3_100k", None, device, lam),

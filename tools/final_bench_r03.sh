@@ -2,8 +2,8 @@
 # round 3: the bench lines with the committed PMC traffic of the same sources (run after tools/final_capture_r03.sh + pmc_summary)
 set -o pipefail
 out=gpurun_out/r03final; mkdir -p $out
-timeout -k 10 400 python bench.py > $out/bal1723_bench.json 2> $out/bal1723_bench.err && echo bal ok
-for w in pose3_100k pose2_100k bal49; do timeout -k 10 300 python bench.py --workload $w > $out/${w}_bench.json 2> $out/${w}_bench.err && echo $w ok; done
+timeout -k 10 400 python bench.py --full > $out/bal1723_bench.json 2> $out/bal1723_bench.err && echo bal ok
+for w in pose3_100k pose2_100k bal49; do timeout -k 10 300 python bench.py --workload $w --full > $out/${w}_bench.json 2> $out/${w}_bench.err && echo $w ok; done
 python - <<PY
 import json
 for w in ("bal1723","pose3_100k","pose2_100k","bal49"):

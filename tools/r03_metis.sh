@@ -1,11 +1,11 @@
 #!/bin/bash
 # round 3: the reference's METIS ordering through the HIP path — parity tests, then ms/step beside the library's ND
 set -e
-mkdir -p gpurun_out/r03
-python -m pytest tests/test_gpu_fullsize.py -x -q -k "metis" > gpurun_out/r03/metis_tests.log 2>&1
+out=${1:-runs/r03}; mkdir -p "$out"
+python -m pytest tests/test_gpu_fullsize.py -x -q -k "metis" > "$out/metis_tests.log" 2>&1
 for wl in bal1723 pose3_100k pose2_100k; do
-  python bench.py --workload $wl --no-cpu-baseline --no-secondary > gpurun_out/r03/${wl}_lib.json 2> gpurun_out/r03/${wl}_lib.err
-  python bench.py --workload $wl --ordering metis --no-cpu-baseline --no-secondary > gpurun_out/r03/${wl}_metis.json 2> gpurun_out/r03/${wl}_metis.err
+  python bench.py --workload $wl --full --no-cpu-baseline --no-secondary > "$out/${wl}_lib.json" 2> "$out/${wl}_lib.err"
+  python bench.py --workload $wl --ordering metis --full --no-cpu-baseline --no-secondary > "$out/${wl}_metis.json" 2> "$out/${wl}_metis.err"
 done
-python bench.py > gpurun_out/r03/default.json 2> gpurun_out/r03/default.err
-tail -3 gpurun_out/r03/metis_tests.log
+python bench.py --full > "$out/default.json" 2> "$out/default.err"
+tail -3 "$out/metis_tests.log"

@@ -1,9 +1,10 @@
 #!/bin/bash
 # usage: tools_prof.sh <outdir-under-gpurun_out> [bench args...]   (run on the GPU box via gpurun)
+root=$(cd "$(dirname "$0")" && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $GRAFT_REPO_ROOT/bench.py "$@" --no-cpu-baseline > $out/bench.json 2> $out/err.log
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 "$root/bench.py" "$@" --full --no-cpu-baseline > $out/bench.json 2> $out/err.log
 python3 - <<PY
 import csv, glob
 f = glob.glob("$out/*/*kernel_stats.csv")[0]
