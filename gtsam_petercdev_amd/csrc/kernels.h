@@ -50,6 +50,21 @@ struct LeafRec {
   int dA, rows, loc, toff;
   int fvar_ptr, front, pad0, pad1;
 };
+// A STAR LEAF (front_star_leaf_kernel): a lean, childless clique whose one frontal variable is of the star group of the
+// H assembly (every BAL landmark, solver.hip: upload_symbolic).  Its factor blocks are read straight from [A b] through
+// the variable's term records (three per factor: own block, partner block, rhs — the first factor's give the shape), 2-row
+// factors at even offsets only; the clique's rows are the panel's (n = panel rows, own rows first, hmap a permutation).
+constexpr int kStarMaxD = 3;
+// The record also carries what cuts the dependent loads of a clique to record -> data: the factors' [A b] offsets when
+// they are evenly spaced (jstride > 0: factor q at jac0 + q jstride — the observations of a landmark stored together; else
+// through the term records) and the clique row of every partner row (prow: a row map per clique, in factor order).
+struct StarLeafRec {  // 88 bytes
+  i64 off, h_off, t0;             // arena L panel, H panel (its rhs row is written), first term record
+  i64 jac0, prow_off;             // first factor's [A b] offset, the clique's partner rows in prow
+  int n, nf, d, toff;             // clique rows, factors, frontal dimension, tangent offset (damping)
+  int colA, colB, colR, dB;       // the factors' shape
+  int front, jstride, rrow, pad0; // front, factor spacing in [A b] (0: uneven), clique row of the rhs
+};
 struct ChildRec {
   i64 src0, cmap_off;   // arena offset of the child's Schur complement (top-left), offset of its row map
   int nc, s1, pad0, pad1;
@@ -210,6 +225,11 @@ void launch_big_schur(const BigDesc* descs, int count, const BigPlan& plan, int 
 void launch_front_leaf(const DevProblem& P, const DevSymbolic& S, const LeafRec* recs, int count, int max_panel, int threads,
                        const double* H, const double* damp, const double* scalars, double* arena, DevStatus* status,
                        hipStream_t st);
+// the star leaves of one launch group (front_star_leaf_kernel): H assembly and front_leaf of those cliques in one pass, same
+// bits; the rhs rows of their H panels are written, the rest of those panels is not
+void launch_front_star_leaf(const DevSymbolic& S, const StarLeafRec* recs, int count, const int* prow, const double* jac,
+                            const double* damp, const double* scalars, double* H, double* arena, DevStatus* status,
+                            hipStream_t st);
 // Deterministic extend-add into big parents (big_gather).
 // A source is either a block of a child's stored Schur complement (F = 0: entry (i, j) at off + i + j ld) or, for a
 // lean leaf child, the product form -W_b W_a' with W_b = rows off.., W_a = rows off + d2.. of the child's n x F L panel.

@@ -1134,6 +1134,26 @@ __global__ void __launch_bounds__(256) assemble_h_diag_kernel(DevProblem P, DevS
   assemble_h_diag_body(P, S, vars, jac, H, blockIdx.x);
 }
 
+// The entries of a star variable's panel, shared by the star assembly below and by front_star_leaf_kernel (which forms
+// them in registers instead of storing them): both must produce the same bits.  Column ci of a factor's [A b] against
+// column cj; a 2-row factor at an even offset loads each column as one 16-byte pair.
+__device__ __forceinline__ double star_pair_dot(double2 x, double2 y) { return x.x * y.x + x.y * y.y; }
+// a partner-block entry: one factor's product
+__device__ __forceinline__ double star_entry(const double* Jf, int m, bool pair, int ci, int cj) {
+  if (pair) return star_pair_dot(reinterpret_cast<const double2*>(Jf)[ci], reinterpret_cast<const double2*>(Jf)[cj]);
+  double acc = 0.0;
+  for (int r = 0; r < m; ++r) acc += Jf[ci * m + r] * Jf[cj * m + r];
+  return acc;
+}
+// an own-block or rhs-row entry: the factor's product added to the running sum over the factors in list order
+__device__ __forceinline__ void star_accum(double& own, const double* Jf, int m, bool pair, int ci, int cj) {
+  if (pair) {
+    own += star_pair_dot(reinterpret_cast<const double2*>(Jf)[ci], reinterpret_cast<const double2*>(Jf)[cj]);
+  } else {
+    for (int r = 0; r < m; ++r) own += Jf[ci * m + r] * Jf[cj * m + r];
+  }
+}
+
 // "Star" variables: every factor of the variable is a binary factor with a LATER-eliminated partner and all factors
 // have the same shape (the landmarks of a bundle adjustment: (camera, point) factors of 2 rows).  The panel is then
 // one off-diagonal block per factor, each written exactly once, plus the variable's own block and the rhs row summed
@@ -1185,33 +1205,12 @@ __global__ void __launch_bounds__(256) assemble_h_star_kernel(DevProblem P, DevS
       const int lo = __shfl((int)(r_jac & 0xffffffff), q), hi = __shfl((int)(r_jac >> 32), q);
       const i64 joff = ((i64)hi << 32) | (unsigned)lo;
       const int dst = __shfl(r_dst, q);
-      if (on) {
-        const double* Jf = jac + joff;
-        double acc;
-        if (m == 2 && (joff & 1) == 0) {
-          const double2 x = reinterpret_cast<const double2*>(Jf)[colB + i];
-          const double2 y = reinterpret_cast<const double2*>(Jf)[colA + j];
-          acc = x.x * y.x + x.y * y.y;
-        } else {
-          acc = 0.0;
-          for (int r = 0; r < m; ++r) acc += Jf[(colB + i) * m + r] * Jf[(colA + j) * m + r];
-        }
-        panel[dst + i + j * rows] = acc;
-      }
+      if (on) panel[dst + i + j * rows] = star_entry(jac + joff, m, m == 2 && (joff & 1) == 0, colB + i, colA + j);
     }
     // own block and rhs row: one lane per entry, over the factors of the chunk in list order
     for (int q = 0; q < nfb; ++q) {
       const i64 joff = readlane_i64(r_jac, q);
-      if (lane < nown) {
-        const double* Jf = jac + joff;
-        if (m == 2 && (joff & 1) == 0) {
-          const double2 x = reinterpret_cast<const double2*>(Jf)[ci];
-          const double2 y = reinterpret_cast<const double2*>(Jf)[cj];
-          own += x.x * y.x + x.y * y.y;
-        } else {
-          for (int r = 0; r < m; ++r) own += Jf[ci * m + r] * Jf[cj * m + r];
-        }
-      }
+      if (lane < nown) star_accum(own, jac + joff, m, m == 2 && (joff & 1) == 0, ci, cj);
     }
   }
   if (lane < nown) panel[odst] = own;
@@ -1285,19 +1284,7 @@ __device__ __forceinline__ void assemble_h_star_bundle_body(const DevProblem& P,
     const int dst = __shfl(r_dst, q);
     const int rows = __shfl(f_rows, q);
     const i64 hoff = ((i64)__shfl((int)(f_hoff >> 32), q) << 32) | (unsigned)__shfl((int)(f_hoff & 0xffffffff), q);
-    if (on) {
-      const double* Jf = jac + joff;
-      double acc;
-      if (m == 2 && (joff & 1) == 0) {
-        const double2 x = reinterpret_cast<const double2*>(Jf)[colB + i];
-        const double2 y = reinterpret_cast<const double2*>(Jf)[colA + j];
-        acc = x.x * y.x + x.y * y.y;
-      } else {
-        acc = 0.0;
-        for (int r = 0; r < m; ++r) acc += Jf[(colB + i) * m + r] * Jf[(colA + j) * m + r];
-      }
-      H[hoff + dst + i + j * rows] = acc;
-    }
+    if (on) H[hoff + dst + i + j * rows] = star_entry(jac + joff, m, m == 2 && (joff & 1) == 0, colB + i, colA + j);
   }
   // own block and rhs row: a lane per (variable, entry), over that variable's factors in list order
   {
@@ -1322,16 +1309,7 @@ __device__ __forceinline__ void assemble_h_star_bundle_body(const DevProblem& P,
     for (int it = 0; it < nfmax; ++it) {
       const int q = min(first + it, 63);
       const i64 joff = ((i64)__shfl((int)(r_jac >> 32), q) << 32) | (unsigned)__shfl((int)(r_jac & 0xffffffff), q);
-      if (on && it < nf) {
-        const double* Jf = jac + joff;
-        if (m == 2 && (joff & 1) == 0) {
-          const double2 x = reinterpret_cast<const double2*>(Jf)[ci];
-          const double2 y = reinterpret_cast<const double2*>(Jf)[cj];
-          own += x.x * y.x + x.y * y.y;
-        } else {
-          for (int r = 0; r < m; ++r) own += Jf[ci * m + r] * Jf[cj * m + r];
-        }
-      }
+      if (on && it < nf) star_accum(own, jac + joff, m, m == 2 && (joff & 1) == 0, ci, cj);
     }
     if (on) H[hoff + odst] = own;
   }
@@ -2757,6 +2735,200 @@ void launch_front_leaf(const DevProblem& P, const DevSymbolic& S, const LeafRec*
   else
     front_leaf_kernel<false><<<count, threads, (size_t)max_panel * sizeof(double), st>>>(P, S, recs, count, 0, H, damp,
                                                                                           scalars, arena, status);
+}
+
+// ---------------------------------------------------------------------------------------------
+// front_star_leaf: the star leaves (kernels.h: StarLeafRec — every BAL landmark) eliminated straight from [A b].  The
+// two-step path (assemble_h_star, then front_leaf) writes the clique's H panel only for front_leaf to read it back once,
+// with three workgroup barriers per pivot; here ONE WAVE per clique forms the panel's entries in registers and eliminates
+// them: no LDS, no barrier, no H panel.  Entry for entry the arithmetic is the two-step path's: a partner entry is
+// star_entry's product, an own-block or rhs entry the products summed over the factors in list order (star_accum),
+// lambda D is added to the own diagonal, and the pivots are front_leaf's (sqrt, inv = 1 / s, x * inv,
+// P[r][c] -= L[r][j] L[c][j] in j order) — same bits.
+//   lanes q < nf:        factor q's own and rhs columns -> its products, summed in factor order through v_readlane;
+//                        then EVERY lane factors the d x d own block itself (uniform values)
+//   lanes p < nf dB:     partner row p (factor p / dB, row p % dB of the partner): its d entries, eliminated, stored at
+//                        the clique row prow[p]
+//   lanes r < d, r = d:  the own rows of L; the rhs row, eliminated — and (J'b)_v into the H panel (model_error_kernel)
+// The first 64 factors' and partner rows' loads are all issued before the first product; with evenly spaced factors
+// (StarLeafRec::jstride) they depend on the record alone.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double readlane_f64(double v, int src_lane) {  // src_lane must be wave-uniform
+  return __longlong_as_double(readlane_i64(__double_as_longlong(v), src_lane));
+}
+// Where the two-step path stores a value (H panel, LDS) and loads it back, this kernel keeps it in a register: the
+// empty asm makes the value opaque there, so that the compiler's contraction cannot fuse a product into the NEXT
+// operation's rounding (fsub(fma(a, b, c * d), e * f) -> fma(a, b, fma(c, d, -e * f))) across what is a store in the
+// two-step path.  It emits no instruction.
+__device__ __forceinline__ void as_stored(double& v) { asm volatile("" : "+v"(v)); }
+__global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, const StarLeafRec* recs, int count,
+                                                              const int* prow, const double* jac, const double* damp,
+                                                              const double* scalars, double* H, double* arena,
+                                                              DevStatus* status) {
+  constexpr int D = kStarMaxD;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (w >= count) return;
+  const StarLeafRec rec = recs[w];
+  const int n = rec.n, nf = rec.nf, d = rec.d, dB = rec.dB;
+  const int colA = rec.colA, colB = rec.colB, colR = rec.colR;
+  const TermRec* T = S.terms + rec.t0;
+  const int* pr = prow + rec.prow_off;
+  // factor q's [A b]: evenly spaced (no load), or from its term record
+  auto factor_jac = [&](int q) {
+    return jac + (rec.jstride > 0 ? rec.jac0 + (i64)q * rec.jstride : T[3 * (i64)q].jac);
+  };
+  const int npart = nf * dB;
+  const float rdB = 1.0f / (float)dB;
+  // factor q's own columns and rhs column (q clamped into range: out-of-range lanes load factor nf - 1 and are never read)
+  auto load_factor = [&](int q, double2* fa, double2& fr) {
+    const double2* J = reinterpret_cast<const double2*>(factor_jac(min(q, nf - 1)));
+#pragma unroll
+    for (int j = 0; j < D; ++j) fa[j] = J[colA + min(j, d - 1)];
+    fr = J[colR];
+  };
+  // partner row p: its clique row, its partner column and the own columns of its factor
+  auto load_row = [&](int p, int& R, double2& xb, double2* ya) {
+    int q, i;
+    p = min(p, npart - 1);
+    divmod_small(p, dB, rdB, q, i);
+    R = pr[p];
+    const double2* J = reinterpret_cast<const double2*>(factor_jac(q));
+    xb = J[colB + i];
+#pragma unroll
+    for (int j = 0; j < D; ++j) ya[j] = J[colA + min(j, d - 1)];
+  };
+  double2 fa[D], fr, xb, ya[D];
+  int R = 0;
+  load_factor(lane, fa, fr);
+  load_row(lane, R, xb, ya);
+  const double lambda = scalars[SC_LAMBDA];
+  // ---- own block (lower triangle) and rhs row: sums over the factors in list order
+  double O[D][D], G[D];
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    G[r] = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) O[r][c] = 0.0;
+  }
+  for (int fb = 0; fb < nf; fb += 64) {
+    if (fb > 0) load_factor(fb + lane, fa, fr);
+    const int nfb = min(64, nf - fb);
+    double po[D][D], pg[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      pg[r] = star_pair_dot(fr, fa[r]);
+#pragma unroll
+      for (int c = 0; c <= r; ++c) po[r][c] = star_pair_dot(fa[r], fa[c]);
+    }
+    for (int q = 0; q < nfb; ++q) {
+#pragma unroll
+      for (int r = 0; r < D; ++r) {
+        if (r >= d) break;
+        G[r] += readlane_f64(pg[r], q);
+#pragma unroll
+        for (int c = 0; c <= r; ++c) O[r][c] += readlane_f64(po[r][c], q);
+      }
+    }
+  }
+  // ---- the own block + lambda D, factored by every lane (front_leaf's pivot sequence)
+  double L[D][D], inv[D];
+  int fail = 0;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+#pragma unroll
+    for (int c = 0; c <= r; ++c) {
+      double x = O[r][c];
+      as_stored(x);
+      if (r == c && r < d) x += lambda * damp[rec.toff + r];
+      as_stored(x);
+      L[r][c] = x;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    if (j >= d) break;
+    const double p = L[j][j];
+    if (!(p > 0)) fail = 1;
+    const double s = (p > 0) ? sqrt(p) : 1.0;
+    inv[j] = 1.0 / s;
+#pragma unroll
+    for (int r = j + 1; r < D; ++r) {
+      L[r][j] = L[r][j] * inv[j];
+      as_stored(L[r][j]);
+    }
+    L[j][j] = s;
+#pragma unroll
+    for (int c = j + 1; c < D; ++c) {
+      const double lc = L[c][j];
+#pragma unroll
+      for (int r = c; r < D; ++r) {
+        L[r][c] -= L[r][j] * lc;
+        as_stored(L[r][c]);
+      }
+    }
+  }
+  // a row below the frontal block: its d entries through the same pivots
+  auto eliminate = [&](double* x) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      if (j >= d) break;
+      x[j] = x[j] * inv[j];
+      as_stored(x[j]);
+#pragma unroll
+      for (int c = j + 1; c < D; ++c) {
+        x[c] -= x[j] * L[c][j];
+        as_stored(x[c]);
+      }
+    }
+  };
+  double* A = arena + rec.off;
+  // ---- partner rows
+  for (int p0 = 0; p0 < npart; p0 += 64) {
+    if (p0 > 0) load_row(p0 + lane, R, xb, ya);
+    double x[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      x[j] = star_pair_dot(xb, ya[j]);
+      as_stored(x[j]);
+    }
+    eliminate(x);
+    if (p0 + lane < npart) {
+#pragma unroll
+      for (int c = 0; c < D; ++c)
+        if (c < d) A[R + (i64)c * n] = x[c];
+    }
+  }
+  // ---- the own rows of L (clique rows 0..d-1) and the rhs row
+  if (lane < d) {
+#pragma unroll
+    for (int r = 0; r < D; ++r)
+      if (lane == r) {
+#pragma unroll
+        for (int c = 0; c <= r; ++c) A[r + (i64)c * n] = L[r][c];
+      }
+  } else if (lane == d) {
+    double x[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      x[j] = G[j];
+      as_stored(x[j]);
+      if (j < d) H[rec.h_off + (n - 1) + (i64)j * n] = G[j];   // (J'b)_v: the rhs row of the H panel
+    }
+    eliminate(x);
+    const int Rg = rec.rrow;
+#pragma unroll
+    for (int c = 0; c < D; ++c)
+      if (c < d) A[Rg + (i64)c * n] = x[c];
+  }
+  // (choleskyPartial's conditioning test runs per reference clique after the factorization: cond_check_kernel)
+  if (fail && lane == 0) report_failure(status, rec.front);
+}
+void launch_front_star_leaf(const DevSymbolic& S, const StarLeafRec* recs, int count, const int* prow, const double* jac,
+                            const double* damp, const double* scalars, double* H, double* arena, DevStatus* status,
+                            hipStream_t st) {
+  if (count)
+    front_star_leaf_kernel<<<(count + 3) / 4, 256, 0, st>>>(S, recs, count, prow, jac, damp, scalars, H, arena, status);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -186,6 +186,22 @@ struct gsx_context {
   std::vector<HGroup> hgroups;
   DevBuf<int2> d_star_bundles;   // bundles of the star group (positions relative to the group's variable list)
   int n_star_bundles = 0;
+  // STAR LEAVES (kernels.hip: front_star_leaf_kernel): the star variables whose clique is a lean leaf are eliminated
+  // straight from [A b] by the factorization, and their H panels are not assembled — only their rhs rows are written (by
+  // that kernel).  GSX_FUSED_STAR=0 at gsx_create: the two-step path (star assembly, then front_leaf).
+  bool fused_star_env = true;    // (read once per handle)
+  bool fused_star = false;       // this tree has star leaves and the handle eliminates them fused
+  bool hstar_ready = true;       // the star group's H panels are complete (false after a fused-mode assembly)
+  struct LeafSplit {
+    int sbegin, scount;          // the launch group's star leaves: range of d_star_recs
+    int rbegin, rcount;          // its other leaves: range of d_leaf_rest_recs
+  };
+  std::vector<LeafSplit> leaf_split;   // per launch group of leaf_launch[0] (fused_star only)
+  DevBuf<StarLeafRec> d_star_recs;
+  DevBuf<int> d_star_prow;       // clique row of every partner row of every star leaf (StarLeafRec::prow_off)
+  DevBuf<LeafRec> d_leaf_rest_recs;
+  DevBuf<int> d_star_rest_vars;  // star variables without a star leaf: assembled as before, one wave each
+  int n_star_rest = 0;
   // numeric buffers
   DevBuf<double> d_values, d_trial, d_delta, d_udelta, d_jac, d_H, d_arena, d_hdiag, d_damp, d_partials, d_scalars;
   DevBuf<double> d_dlu, d_dld;  // Dogleg: steepest-descent point, dog-leg point (allocated on first use)
@@ -1037,6 +1053,81 @@ gsx_status upload_symbolic(gsx_context* c) {
     c->GA = GatherArgs{c->d_gsegs.p, c->d_gsrcs.p, c->d_gt_dst.p, c->d_gt_ld.p, c->d_gt_dims.p, c->d_gm_task.p,
                        c->d_gm_slot.p, c->d_gm_nslots.p, c->d_gscratch.p};
   }
+  // ---- star leaves: lean childless cliques of one star variable, every factor 2 rows at an even [A b] offset, the
+  //      clique's rows those of the panel (own rows first) ----
+  c->fused_star = false;
+  c->leaf_split.clear();
+  c->n_star_rest = 0;
+  {
+    int sgrp = -1;
+    for (size_t g = 0; g < c->hgroups.size(); ++g)
+      if (c->hgroups[g].threads == -1) sgrp = (int)g;
+    if (c->fused_star_env && sgrp >= 0 && !c->sharded() && !c->constrained() && S.n_levels > 0) {
+      auto star_leaf = [&](const LeafRec& r) {
+        const int v = S.fvars[S.fvar_ptr[r.front]];
+        if (c->hv_group_of_var[v] != sgrp || r.nfv != 1 || !r.lean || r.F != r.dA || r.dA > kStarMaxD || r.loc != 0 ||
+            r.n != r.rows)
+          return false;
+        const int64_t tb = S.term_ptr[v], te = S.term_ptr[v + 1];
+        const int64_t nf = (te - tb) / 3;
+        if (nf < 1 || nf >= 1024 || r.dA + nf * S.t_dB[tb + 1] + 1 != r.n) return false;
+        for (int64_t t = tb; t < te; t += 3)
+          if (S.t_m[t] != 2 || (S.t_jac[t] & 1)) return false;
+        std::vector<char> seen(r.n, 0);
+        for (int k = 0; k < r.n; ++k) {
+          const int R = S.hmap[S.hmap_ptr[v] + k];
+          if (R < 0 || R >= r.n || seen[R] || (k < r.dA && R != k)) return false;
+          seen[R] = 1;
+        }
+        return true;
+      };
+      std::vector<char> fused_var(P.n_vars, 0);
+      std::vector<StarLeafRec> srec;
+      std::vector<int> prow;
+      std::vector<LeafRec> rrec;
+      for (const SmallLaunch& sl : c->leaf_launch[0]) {
+        gsx_context::LeafSplit ls{(int)srec.size(), 0, (int)rrec.size(), 0};
+        for (int k = sl.begin; k < sl.begin + sl.count; ++k) {
+          const LeafRec& r = c->h_leaf_recs[k - c->leaf_base];
+          if (!star_leaf(r)) {
+            rrec.push_back(r);
+            continue;
+          }
+          const int v = S.fvars[S.fvar_ptr[r.front]];
+          const int64_t tb = S.term_ptr[v];
+          const int nf = (int)((S.term_ptr[v + 1] - tb) / 3), dB = S.t_dB[tb + 1];
+          fused_var[v] = 1;
+          const int64_t stride = nf > 1 ? S.t_jac[tb + 3] - S.t_jac[tb] : 2;
+          bool even = stride > 0 && stride <= (1 << 30);
+          for (int q = 0; q < nf && even; ++q) even = S.t_jac[tb + 3 * q] == S.t_jac[tb] + q * stride;
+          const int* hm = S.hmap.data() + S.hmap_ptr[v];
+          const i64 prow_off = (i64)prow.size();
+          for (int q = 0; q < nf; ++q)
+            for (int i = 0; i < dB; ++i) prow.push_back(hm[S.t_dst[tb + 3 * q + 1] + i]);
+          srec.push_back(StarLeafRec{r.off, r.h_off, (i64)tb, (i64)S.t_jac[tb], prow_off, r.n, nf, r.dA, r.toff,
+                                     S.t_colA[tb], S.t_colB[tb + 1], S.t_colB[tb + 2], dB, r.front, even ? (int)stride : 0,
+                                     hm[r.n - 1], 0});
+        }
+        ls.scount = (int)srec.size() - ls.sbegin;
+        ls.rcount = (int)rrec.size() - ls.rbegin;
+        c->leaf_split.push_back(ls);
+      }
+      if (!srec.empty()) {
+        std::vector<int> rest;
+        const gsx_context::HGroup& g = c->hgroups[sgrp];
+        for (int k = g.begin; k < g.begin + g.count; ++k)
+          if (!fused_var[c->hv_list[k]]) rest.push_back(c->hv_list[k]);
+        c->fused_star = true;
+        c->n_star_rest = (int)rest.size();
+        HIPCHK(c, c->d_star_recs.upload(srec, st));
+        HIPCHK(c, c->d_star_prow.upload(prow, st));
+        if (!rrec.empty()) HIPCHK(c, c->d_leaf_rest_recs.upload(rrec, st));
+        if (!rest.empty()) HIPCHK(c, c->d_star_rest_vars.upload(rest, st));
+      } else {
+        c->leaf_split.clear();
+      }
+    }
+  }
   DevSymbolic& D = c->DS;
   D.n_fronts = S.n_fronts;
   D.fr_off = c->d_fr_off.p; D.fr_N = c->d_fr_N.p; D.fr_F = c->d_fr_F.p; D.fr_nfv = c->d_fr_nfv.p;
@@ -1101,12 +1192,20 @@ void dev_assemble_h(gsx_context* c) {
     if (g.threads == -1 && c->n_star_bundles) gs = &g;
     if (g.threads == 0 && g.count > 0) gd = &g;
   }
-  const bool fused = gs && gd;
+  // (star leaves: their panels are formed by the factorization itself — front_star_leaf_kernel; dev_ensure_hstar)
+  const bool fs = c->fused_star;
+  const bool fused = gs && gd && !fs;
   if (fused)
     launch_assemble_h_diag_star(c->DP, c->DS, c->d_hvars.p + gd->begin, gd->count, c->d_hvars.p + gs->begin,
                                 c->d_star_bundles.p, c->n_star_bundles, c->d_jac.p, c->d_H.p, c->stream);
   for (const auto& g : c->hgroups) {
     if (fused && (&g == gs || &g == gd)) continue;
+    if (fs && g.threads == -1) {
+      if (c->n_star_rest)
+        launch_assemble_h_group(c->DP, c->DS, c->d_star_rest_vars.p, c->n_star_rest, -1, 0, false, c->d_jac.p, c->d_H.p,
+                                c->stream);
+      continue;
+    }
     if (g.threads == -1 && c->n_star_bundles) {  // the whole star group, a wave per bundle of variables
       launch_assemble_h_star_bundles(c->DP, c->DS, c->d_hvars.p + g.begin, c->d_star_bundles.p, c->n_star_bundles,
                                      c->d_jac.p, c->d_H.p, c->stream);
@@ -1117,11 +1216,29 @@ void dev_assemble_h(gsx_context* c) {
   }
   timer_end(c, PH_ASSEMBLE_H);
   c->h_ready = true;
+  c->hstar_ready = !fs;
   c->hdiag_ready = false;  // diag(H) is extracted on demand: lambda * I damping never needs it
+}
+
+// The complete H panels of the star group, for the readers other than the factorization (diag(H), the gradient, the
+// filtered front_leaf launches of gsx_relinearize_partial) after an assembly that left the star leaves' panels out.
+void dev_ensure_hstar(gsx_context* c) {
+  if (c->hstar_ready) return;
+  for (const auto& g : c->hgroups) {
+    if (g.threads != -1) continue;
+    if (c->n_star_bundles)
+      launch_assemble_h_star_bundles(c->DP, c->DS, c->d_hvars.p + g.begin, c->d_star_bundles.p, c->n_star_bundles,
+                                     c->d_jac.p, c->d_H.p, c->stream);
+    else
+      launch_assemble_h_group(c->DP, c->DS, c->d_hvars.p + g.begin, g.count, g.threads, g.lds, g.global, c->d_jac.p,
+                              c->d_H.p, c->stream);
+  }
+  c->hstar_ready = true;
 }
 
 void dev_hessian_diag(gsx_context* c) {
   if (c->hdiag_ready) return;
+  dev_ensure_hstar(c);
   launch_hessian_diag(c->DP, c->DS, c->d_H.p, c->d_hdiag.p, c->stream);
   if (c->con_hd_n)
     launch_constraint_hdiag(c->con_hd_n, c->d_con_hd_tan.p, c->d_con_hd_ptr.p, c->d_con_hd_jidx.p, c->d_con_hd_w.p,
@@ -1174,6 +1291,22 @@ void debug_sync(gsx_context* c, const char* what, int a, int b) {
   fflush(stderr);
 }
 
+// one launch group of the leaf-kernel cliques: its star leaves fused (front_star_leaf_kernel), the others by front_leaf
+void dev_leaf_group(gsx_context* c, size_t g, hipStream_t st) {
+  const SmallLaunch& sl = c->leaf_launch[0][g];
+  if (c->fused_star && c->leaf_split[g].scount) {
+    const gsx_context::LeafSplit& ls = c->leaf_split[g];
+    launch_front_star_leaf(c->DS, c->d_star_recs.p + ls.sbegin, ls.scount, c->d_star_prow.p, c->d_jac.p, c->d_damp.p,
+                           c->d_scalars.p, c->d_H.p, c->d_arena.p, c->d_status.p, st);
+    if (ls.rcount)
+      launch_front_leaf(c->DP, c->DS, c->d_leaf_rest_recs.p + ls.rbegin, ls.rcount, sl.max_panel, sl.threads, c->d_H.p,
+                        c->d_damp.p, c->d_scalars.p, c->d_arena.p, c->d_status.p, st);
+    return;
+  }
+  launch_front_leaf(c->DP, c->DS, c->d_leaf_recs.p + (sl.begin - c->leaf_base), sl.count, sl.max_panel, sl.threads, c->d_H.p,
+                    c->d_damp.p, c->d_scalars.p, c->d_arena.p, c->d_status.p, st);
+}
+
 // the low-priority queue of the side work (created on first use)
 bool bulk_ready(gsx_context* c) {
   if (c->bulk) return true;
@@ -1219,21 +1352,15 @@ void dev_factorize(gsx_context* c, double lambda) {
       //  earlier, what is lost is every kernel running beside them running slower.)
       hipEventRecord(c->bulk_go, c->stream);
       hipStreamWaitEvent(c->bulk, c->bulk_go, 0);
-      for (size_t g = n_main_leaf; g < LL.size(); ++g) {
-        const SmallLaunch& sl = LL[g];
-        launch_front_leaf(c->DP, c->DS, c->d_leaf_recs.p + (sl.begin - c->leaf_base), sl.count, sl.max_panel, sl.threads,
-                          c->d_H.p, c->d_damp.p, c->d_scalars.p, c->d_arena.p, c->d_status.p, c->bulk);
-      }
+      for (size_t g = n_main_leaf; g < LL.size(); ++g) dev_leaf_group(c, g, c->bulk);
       launch_big_gather(c->GA, S.gseg_lvl_ptr[sg], S.gseg_lvl_ptr[sg + 1] - S.gseg_lvl_ptr[sg], S.gm_lvl_ptr[sg],
                         S.gm_lvl_ptr[sg + 1] - S.gm_lvl_ptr[sg], c->d_arena.p, c->bulk);
       hipEventRecord(c->bulk_done, c->bulk);
       c->bulk_pending = true;
     }
     for (size_t g = 0; g < (use_bulk ? n_main_leaf : LL.size()); ++g) {
-      const SmallLaunch& sl = LL[g];
       if (c->profiling > 0) timer_begin(c, PH_FACTOR_LEAF);
-      launch_front_leaf(c->DP, c->DS, c->d_leaf_recs.p + (sl.begin - c->leaf_base), sl.count, sl.max_panel, sl.threads, c->d_H.p,
-                        c->d_damp.p, c->d_scalars.p, c->d_arena.p, c->d_status.p, c->stream);
+      dev_leaf_group(c, g, c->stream);
       if (c->profiling > 0) timer_end(c, PH_FACTOR_LEAF);
     }
   }
@@ -1645,6 +1772,10 @@ gsx_status gsx_create(const gsx_problem_desc* desc, int32_t device, gsx_handle* 
     return st;
   }
   c->device = device;
+  {
+    const char* e = std::getenv("GSX_FUSED_STAR");
+    c->fused_star_env = !(e && std::atoi(e) == 0);
+  }
   int n = 0;
   if (hipGetDeviceCount(&n) == hipSuccess && n > 0 && device >= 0 && device < n && hipSetDevice(device) == hipSuccess &&
       hipStreamCreate(&c->stream) == hipSuccess) {
@@ -2298,6 +2429,7 @@ gsx_status gsx_dogleg_optimize(gsx_handle h, double delta_initial, int32_t max_i
       dev_damping(h, 0, 0, 0);
       dev_factorize(h, 0.0);
       dev_backsolve(h);  // d_delta = Newton point dx_n
+      dev_ensure_hstar(h);
       // steepest-descent point: grad = -A'b = -g, dx_u = -(grad'grad / |A grad|^2) grad = (g'g / |A g|^2) g
       launch_gradient(h->DP, h->DS, h->d_H.p, h->d_dlu.p, h->stream);
       launch_vec_dot(h->d_dlu.p, h->d_dlu.p, nt, h->d_partials.p, gsx_context::kPartials, h->d_scalars.p, SC_DOT0, h->stream);
@@ -2417,6 +2549,7 @@ gsx_status partial_linearize(gsx_handle h, std::vector<int>& dfac) {
 gsx_status partial_assemble(gsx_handle h, std::vector<int>& dvar) {
   hipStream_t sm = h->stream;
   gsx_context::PartialScratch& ps = h->ps;
+  dev_ensure_hstar(h);   // (the filtered front_leaf launches of partial_factor read the star leaves' panels)
   {
     std::sort(dvar.begin(), dvar.end(), [&](int a, int b) { return h->hv_pos[a] < h->hv_pos[b]; });
     std::vector<std::pair<int, int>> ranges(h->hgroups.size(), {0, 0});
