@@ -397,6 +397,35 @@ class Backend:
                     "joint_marginal_covariance")
         return out.reshape(D, D)
 
+    def marginal_blocks_size(self, keys=None) -> int:
+        """Doubles marginal_covariances(keys) returns in all: the sum of d_v * d_v; -1 for an unknown or repeated key."""
+        if self._pfx != "gsx_":
+            raise NotImplementedError("marginal_covariances is an entry point of the product backend")
+        if keys is None:
+            return int(self._fn("marginal_blocks_size", C.c_int64)(self._h, None, C.c_int32(0)))
+        ks = np.ascontiguousarray(keys, dtype=np.uint64)
+        return int(self._fn("marginal_blocks_size", C.c_int64)(self._h, ks.ctypes.data_as(_p(C.c_uint64)),
+                                                               C.c_int32(ks.size)))
+
+    def marginal_covariances(self, keys=None) -> dict:
+        """The marginal covariance blocks of the listed variables (None: every variable) from one top-down pass over the
+        device factorization: {key: d x d}."""
+        n = self.marginal_blocks_size(keys)
+        if keys is None:
+            ks, kp, nk = self.arrays.var_keys, None, 0
+        else:
+            ks = np.ascontiguousarray(keys, dtype=np.uint64)
+            kp, nk = ks.ctypes.data_as(_p(C.c_uint64)), int(ks.size)
+        out = np.zeros(max(n, 1))
+        self._check(self._fn("marginal_covariances")(self._h, kp, C.c_int32(nk), out.ctypes.data_as(_p(C.c_double)),
+                                                     C.c_int64(n)), "marginal_covariances")
+        res, o = {}, 0
+        for k in ks:
+            d = int(self.arrays.var_dims[int(np.searchsorted(self.arrays.var_keys, k))])
+            res[int(k)] = out[o:o + d * d].reshape(d, d).T.copy()  # column-major
+            o += d * d
+        return res
+
     def dogleg_optimize(self, delta_initial=1.0, max_iterations=100, relative_error_tol=1e-5, absolute_error_tol=1e-5,
                         error_tol=0.0, trace_cap=4096):
         """DoglegOptimizer (ONE_STEP_PER_ITERATION); trace_lambda / final_lambda carry the trust-region radius."""

@@ -305,6 +305,28 @@ void launch_vec_axpby(double* out, double alpha, const double* a, double beta, c
 void launch_marginal_path(const DevSymbolic& S, const int* path, int npath, int loc, int dA, int max_n, const double* arena,
                           double* out, double* Y, int64_t n_tan, hipStream_t st);
 void launch_joint_cross(const double* Ya, const double* Yb, int64_t n_tan, int dA, int dB, double* out, hipStream_t st);
+// Marginal covariances of all variables in one top-down pass (marginals.hip).  Every front of class 1 or 2 owns a block
+// of the covariance arena: its (n - 1) x (n - 1) Sigma over [frontal | separator] rows (column-major, lower triangle
+// significant) and a work area of F (n - 1) doubles (X' = L11^-T, then Kt = L21 X).  Per level, from the top: prep
+// (X' and the gather of Sigma_SS from the parent's block), kt, sf, ff — one work item per workgroup; then the diagonal
+// blocks of the variables (emit) and, last, the leaf-kernel cliques (class 0), which own no block.
+struct MargItem {   // 16 bytes
+  int front, ti, tj, pad;   // 32 x 32 tile (ti, tj) of the step's result; prep: ti < 0 = the inverse, else 32 separator rows
+};
+struct MargArgs {
+  const i64 *slot, *work;   // per front: doubles into `cov` (-1: a class-0 front)
+  double* cov;
+  const double* arena;
+  const i64* out_off;       // per variable: doubles into `out`, -1: not asked for
+  const int* var_dim;
+  double* out;
+};
+void launch_marg_prep(const DevSymbolic& S, const MargArgs& M, const MargItem* items, int count, hipStream_t st);
+void launch_marg_kt(const DevSymbolic& S, const MargArgs& M, const MargItem* items, int count, hipStream_t st);
+void launch_marg_sf(const DevSymbolic& S, const MargArgs& M, const MargItem* items, int count, hipStream_t st);
+void launch_marg_ff(const DevSymbolic& S, const MargArgs& M, const MargItem* items, int count, hipStream_t st);
+void launch_marg_emit(const DevSymbolic& S, const MargArgs& M, const int2* vars, int count, hipStream_t st);
+void launch_marg_leaf(const DevSymbolic& S, const MargArgs& M, const int* ids, int count, hipStream_t st);
 void launch_set_scalar(double* scalars, int slot, double v, hipStream_t st);
 // Hard constraints (constraint.hip): one record per constrained front (Symbolic::con_fronts order, children first)
 struct ConDesc {

@@ -84,10 +84,12 @@ struct BigLevel {
 
 enum Phase { PH_LINEARIZE, PH_ASSEMBLE_H, PH_FACTORIZE, PH_BACKSOLVE, PH_LINERR, PH_RETRACT, PH_ERROR,
              PH_FACTOR_SMALL, PH_FACTOR_BIG, PH_FACTOR_LEAF, PH_K_SYRK, PH_K_TRSM, PH_K_POTRF0, PH_K_GATHER,
-             PH_K_BACKSOLVE, PH_COUNT };
+             PH_K_BACKSOLVE, PH_MARGINALS, PH_M_PREP, PH_M_KT, PH_M_SF, PH_M_FF, PH_M_EMIT, PH_M_LEAF, PH_COUNT };
 const char* kPhaseNames[PH_COUNT] = {"linearize", "assemble_hessian", "factorize", "backsolve", "linear_error",
                                      "retract", "error", "factor_small", "factor_big", "factor_leaf",
-                                     "big_schur", "big_rows", "big_diag", "big_gather", "backsolve_launch"};
+                                     "big_schur", "big_rows", "big_diag", "big_gather", "backsolve_launch",
+                                     "all_marginals", "marg_prep", "marg_kt", "marg_sf", "marg_ff", "marg_emit",
+                                     "marg_leaf"};
 
 struct Timer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, pool;
@@ -202,6 +204,44 @@ struct gsx_context {
   DevBuf<LeafRec> d_leaf_rest_recs;
   DevBuf<int> d_star_rest_vars;  // star variables without a star leaf: assembled as before, one wave each
   int n_star_rest = 0;
+  // marginal covariances of all variables (gsx_marginal_covariances; marginals.hip): the covariance arena and the work
+  // lists of the whole tree, made on first use and dropped whenever the tree changes (upload_symbolic)
+  struct MargLevel {
+    int begin[4], count[4];          // ranges of d_items per step: prep, kt, sf, ff
+  };
+  struct MargPlan {
+    std::vector<MargLevel> levels;   // top level first
+    DevBuf<MargItem> d_items;
+    DevBuf<int2> d_emit;             // (variable, front) of the asked variables whose front owns a block
+    DevBuf<int> d_leaves;            // the leaf-kernel cliques with an asked variable
+    DevBuf<i64> d_out_off;
+    int n_emit = 0, n_leaves = 0;
+    int64_t total = 0;
+    bool ready = false;
+    void release() {
+      levels.clear();
+      d_items.release();
+      d_emit.release();
+      d_leaves.release();
+      d_out_off.release();
+      n_emit = n_leaves = 0;
+      total = 0;
+      ready = false;
+    }
+  };
+  MargPlan marg_all;
+  DevBuf<i64> d_marg_slot, d_marg_work;
+  DevBuf<double> d_marg_cov;
+  bool marg_arena = false;
+  int64_t marg_cov_doubles = 0;
+  void marg_release() {
+    marg_all.release();
+    d_marg_slot.release();
+    d_marg_work.release();
+    d_marg_cov.release();
+    marg_arena = false;
+    marg_cov_doubles = 0;
+  }
   // numeric buffers
   DevBuf<double> d_values, d_trial, d_delta, d_udelta, d_jac, d_H, d_arena, d_hdiag, d_damp, d_partials, d_scalars;
   DevBuf<double> d_dlu, d_dld;  // Dogleg: steepest-descent point, dog-leg point (allocated on first use)
@@ -516,6 +556,7 @@ gsx_status upload_symbolic(gsx_context* c) {
   const Symbolic& S = c->S;
   const HostProblem& P = c->P;
   hipStream_t st = c->stream;
+  c->marg_release();   // (sized and listed by the tree that is being replaced)
   HIPCHK(c, c->d_fr_off.upload(std::vector<i64>(S.off.begin(), S.off.end()), st));
   HIPCHK(c, c->d_fr_N.upload(S.N, st));
   HIPCHK(c, c->d_fr_F.upload(S.F, st));
@@ -3202,6 +3243,205 @@ gsx_status gsx_marginal_covariance(gsx_handle h, uint64_t key, double* out, int6
   return GSX_OK;
 }
 
+namespace {
+// the covariance arena of the current tree: a block and a work area per front of class 1 or 2 (kernels.h: MargArgs)
+gsx_status marg_arena_ready(gsx_context* c) {
+  if (c->marg_arena) return GSX_OK;
+  const Symbolic& S = c->S;
+  std::vector<i64> slot(std::max(S.n_fronts, 1), -1), work(std::max(S.n_fronts, 1), -1);
+  i64 cur = 0;
+  for (int f = 0; f < S.n_fronts; ++f) {
+    if (S.cls[f] == 0) continue;
+    const i64 m = S.N[f] - 1;
+    slot[f] = cur;
+    cur += m * m;
+    work[f] = cur;
+    cur += (i64)S.F[f] * m;
+  }
+  HIPCHK(c, c->d_marg_slot.upload(slot, c->stream));
+  HIPCHK(c, c->d_marg_work.upload(work, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->d_marg_cov.alloc((size_t)std::max<i64>(cur, 1)) != hipSuccess) {
+    (void)hipGetLastError();
+    c->d_marg_cov.p = nullptr;
+    c->d_marg_cov.n = 0;
+    c->err = "marginal covariances: the covariance arena (" + std::to_string(8.0 * (double)cur / 1e9) + " GB) does not fit";
+    return GSX_E_NOMEM;
+  }
+  c->marg_cov_doubles = cur;
+  c->marg_arena = true;
+  return GSX_OK;
+}
+
+// Work lists for the variables `vars` (output order); all: every variable, else only the fronts on their paths to the root.
+gsx_status marg_build_plan(gsx_context* c, const std::vector<int>& vars, bool all, gsx_context::MargPlan& plan) {
+  const Symbolic& S = c->S;
+  const HostProblem& P = c->P;
+  plan.release();
+  std::vector<i64> out_off(std::max(P.n_vars, 1), -1);
+  for (int v : vars) {
+    out_off[v] = plan.total;
+    plan.total += (int64_t)P.dims[v] * P.dims[v];
+  }
+  std::vector<char> need(S.n_fronts, all ? 1 : 0);
+  if (!all)
+    for (int v : vars)
+      for (int f = S.front_of_var[v]; f >= 0 && !need[f]; f = S.parent[f]) need[f] = 1;
+  int n_levels = 0;
+  for (int f = 0; f < S.n_fronts; ++f) n_levels = std::max(n_levels, S.level[f] + 1);
+  std::vector<std::vector<int>> by_level(n_levels);
+  for (int f = 0; f < S.n_fronts; ++f)
+    if (need[f] && S.cls[f] != 0) by_level[S.level[f]].push_back(f);
+  std::vector<int2> emit;
+  std::vector<int> leaves;
+  {
+    std::vector<char> listed(S.n_fronts, 0);
+    for (int v : vars) {
+      const int f = S.front_of_var[v];
+      if (S.cls[f] != 0) emit.push_back(make_int2(v, f));
+      else if (!listed[f]) {
+        listed[f] = 1;
+        leaves.push_back(f);
+      }
+    }
+  }
+  std::vector<MargItem> items, step[4];
+  for (int lvl = n_levels - 1; lvl >= 0; --lvl) {
+    if (by_level[lvl].empty()) continue;
+    for (auto& sv : step) sv.clear();
+    for (int f : by_level[lvl]) {
+      const int F = S.F[f], s = S.N[f] - 1 - F;
+      const int tf = (F + 31) / 32, ts = (s + 31) / 32;
+      step[0].push_back(MargItem{f, -1, 0, 0});
+      for (int ti = 0; ti < ts; ++ti) step[0].push_back(MargItem{f, ti, 0, 0});
+      for (int tj = 0; tj < tf; ++tj)
+        for (int ti = 0; ti < ts; ++ti) {
+          step[1].push_back(MargItem{f, ti, tj, 0});
+          step[2].push_back(MargItem{f, ti, tj, 0});
+        }
+      for (int tj = 0; tj < tf; ++tj)
+        for (int ti = tj; ti < tf; ++ti) step[3].push_back(MargItem{f, ti, tj, 0});
+    }
+    gsx_context::MargLevel L;
+    for (int k = 0; k < 4; ++k) {
+      L.begin[k] = (int)items.size();
+      L.count[k] = (int)step[k].size();
+      items.insert(items.end(), step[k].begin(), step[k].end());
+    }
+    plan.levels.push_back(L);
+  }
+  if (items.size() > (size_t)INT_MAX) {
+    c->err = "marginal covariances: too many tiles";
+    return GSX_E_NOMEM;
+  }
+  plan.n_emit = (int)emit.size();
+  plan.n_leaves = (int)leaves.size();
+  HIPCHK(c, plan.d_items.upload(items, c->stream));
+  HIPCHK(c, plan.d_emit.upload(emit, c->stream));
+  HIPCHK(c, plan.d_leaves.upload(leaves, c->stream));
+  HIPCHK(c, plan.d_out_off.upload(out_off, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host vectors go out of scope)
+  plan.ready = true;
+  return GSX_OK;
+}
+
+extern "C++" {
+template <class Fn>
+void marg_timed(gsx_context* c, int ph, Fn launch) {
+  if (c->profiling > 0) timer_begin(c, ph);
+  launch();
+  if (c->profiling > 0) timer_end(c, ph);
+}
+}
+
+gsx_status marg_run(gsx_context* c, const gsx_context::MargPlan& plan, double* out) {
+  DevBuf<double> d_out;
+  HIPCHK(c, d_out.alloc((size_t)std::max<int64_t>(plan.total, 1)));
+  const MargArgs M{c->d_marg_slot.p, c->d_marg_work.p, c->d_marg_cov.p, c->d_arena.p, plan.d_out_off.p, c->d_var_dim.p, d_out.p};
+  hipStream_t st = c->stream;
+  const MargItem* items = plan.d_items.p;
+  timer_begin(c, PH_MARGINALS);
+  for (const gsx_context::MargLevel& L : plan.levels) {
+    marg_timed(c, PH_M_PREP, [&] { launch_marg_prep(c->DS, M, items + L.begin[0], L.count[0], st); });
+    marg_timed(c, PH_M_KT, [&] { launch_marg_kt(c->DS, M, items + L.begin[1], L.count[1], st); });
+    marg_timed(c, PH_M_SF, [&] { launch_marg_sf(c->DS, M, items + L.begin[2], L.count[2], st); });
+    marg_timed(c, PH_M_FF, [&] { launch_marg_ff(c->DS, M, items + L.begin[3], L.count[3], st); });
+  }
+  marg_timed(c, PH_M_EMIT, [&] { launch_marg_emit(c->DS, M, plan.d_emit.p, plan.n_emit, st); });
+  marg_timed(c, PH_M_LEAF, [&] { launch_marg_leaf(c->DS, M, plan.d_leaves.p, plan.n_leaves, st); });
+  timer_end(c, PH_MARGINALS);
+  if (plan.total) HIPCHK(c, hipMemcpyAsync(out, d_out.p, (size_t)plan.total * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  return GSX_OK;
+}
+
+// the variables of a key list (nullptr: all, ascending key order = variable order); -1 for an unknown or repeated key
+int64_t marg_key_vars(gsx_context* c, const uint64_t* keys, int32_t n_keys, std::vector<int>* vars) {
+  const HostProblem& P = c->P;
+  int64_t total = 0;
+  if (!keys) {
+    for (int v = 0; v < P.n_vars; ++v) {
+      if (vars) vars->push_back(v);
+      total += (int64_t)P.dims[v] * P.dims[v];
+    }
+    return total;
+  }
+  if (n_keys < 0) return -1;
+  std::vector<char> seen(std::max(P.n_vars, 1), 0);
+  for (int k = 0; k < n_keys; ++k) {
+    const int v = find_var(c, keys[k]);
+    if (v < 0 || seen[v]) return -1;
+    seen[v] = 1;
+    if (vars) vars->push_back(v);
+    total += (int64_t)P.dims[v] * P.dims[v];
+  }
+  return total;
+}
+
+static gsx_status gsx_marginal_covariances_impl(gsx_handle h, const uint64_t* keys, int32_t n_keys, double* out, int64_t n_out) {
+  if (!h || (!out && n_out != 0)) return GSX_E_INVALID;
+  std::vector<int> vars;
+  const int64_t total = marg_key_vars(h, keys, n_keys, &vars);
+  if (total < 0) {
+    h->err = "marginals of a key list with an unknown or repeated key";
+    return GSX_E_INVALID;
+  }
+  if (n_out != total) {
+    h->err = "marginals: n_out differs from gsx_marginal_blocks_size";
+    return GSX_E_INVALID;
+  }
+  gsx_status st = marginals_prepare(h);
+  if (st != GSX_OK) return st;
+  if (h->constrained()) {
+    h->err = "marginal covariances are not available on a problem with hard constraints";
+    return GSX_E_STATE;
+  }
+  st = marg_arena_ready(h);
+  if (st != GSX_OK) return st;
+  if (!keys) {
+    if (!h->marg_all.ready) {
+      st = marg_build_plan(h, vars, true, h->marg_all);
+      if (st != GSX_OK) return st;
+    }
+    return marg_run(h, h->marg_all, out);
+  }
+  gsx_context::MargPlan plan;
+  st = marg_build_plan(h, vars, false, plan);
+  if (st != GSX_OK) return st;
+  return marg_run(h, plan, out);
+}
+}  // namespace
+
+int64_t gsx_marginal_blocks_size(gsx_handle h, const uint64_t* keys, int32_t n_keys) {
+  if (!h) return -1;
+  try {
+    return marg_key_vars(h, keys, n_keys, nullptr);
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+
 static gsx_status gsx_set_block_jacobians_impl(gsx_handle h, int32_t first_factor, int32_t n_factors, const double* values,
                                    int64_t n_values) {
   if (!h || !values || first_factor < 0 || n_factors < 0 || (int64_t)first_factor + (int64_t)n_factors > (int64_t)h->P.n_factors) return GSX_E_INVALID;
@@ -3386,6 +3626,9 @@ gsx_status gsx_cholesky_partial(double* abc, int32_t n, int32_t nfrontal, int32_
 gsx_status gsx_set_block_jacobians(gsx_handle h, int32_t first_factor, int32_t n_factors, const double* values,
                                    int64_t n_values) {
   GSX_GUARD(h, gsx_set_block_jacobians_impl(h, first_factor, n_factors, values, n_values));
+}
+gsx_status gsx_marginal_covariances(gsx_handle h, const uint64_t* keys, int32_t n_keys, double* out, int64_t n_out) {
+  GSX_GUARD(h, gsx_marginal_covariances_impl(h, keys, n_keys, out, n_out));
 }
 gsx_status gsx_update(gsx_handle h, const gsx_problem_desc* desc, const int32_t* factor_origin, const double* new_values,
                       int64_t n_new_values, gsx_update_stats* out) {

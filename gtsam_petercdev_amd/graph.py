@@ -763,9 +763,20 @@ class Marginals:
             ordering = self.backend.compute_ordering(kind)
         self.backend.set_ordering([int(k) for k in ordering])
         self.backend.linearize()
+        self._blocks = {}
 
     def marginalCovariance(self, key):
+        if int(key) in self._blocks:
+            return self._blocks[int(key)].copy()
         return self.backend.marginal_covariance(key)
+
+    def marginalCovariances(self, keys=None) -> dict:
+        """The marginal covariance of every listed variable (None: all of them) as {key: d x d}, from one top-down pass
+        over the device factorization instead of one query per variable; marginalCovariance(key) serves from the
+        result afterwards (a Marginals object stands for one fixed linearization, as the reference's does)."""
+        res = self.backend.marginal_covariances(None if keys is None else [int(k) for k in keys])
+        self._blocks.update(res)
+        return {k: v.copy() for k, v in res.items()}
 
     def marginalInformation(self, key):
         return np.linalg.inv(self.marginalCovariance(key))

@@ -464,6 +464,21 @@ gsx_status gsx_marginal_covariance(gsx_handle h, uint64_t key, double* out, int6
  * variables, D x D row-major with D = sum of their dimensions, blocks in the order of `keys` (the reference returns
  * them sorted by key: pass sorted keys for the same layout). */
 gsx_status gsx_joint_marginal_covariance(gsx_handle h, const uint64_t* keys, int32_t n_keys, double* out, int64_t n_out);
+/* Marginal covariances of MANY variables in one top-down pass over the undamped factorization (selected inversion: each
+ * clique's block of H^-1 from its parent's, every clique of a level in parallel; the reference shares the same work through
+ * the cached separator marginals of its Bayes tree, gtsam/inference/BayesTreeCliqueBase-inst.h).
+ * gsx_marginal_blocks_size: the doubles gsx_marginal_covariances writes for these keys, the sum of d_v * d_v
+ * (keys == NULL: every variable; n_keys is then ignored).  -1 for a NULL handle, a negative n_keys, an unknown key or a key
+ * listed twice (the cases gsx_marginal_covariances answers with GSX_E_INVALID).  Needs no device.
+ * gsx_marginal_covariances: the d_v x d_v blocks of H^-1 (column-major, tangent space, current linearization) of the listed
+ * variables, one after the other in the order of `keys`; keys == NULL: every variable in ascending key order.  For a key
+ * list only the cliques on the listed variables' paths to the root are visited; the blocks are the same bits as those of
+ * the all-variables call.  No limit on n_keys or on the dimension of a variable.  GSX_E_INVALID: unknown or repeated key,
+ * n_out != gsx_marginal_blocks_size; GSX_E_STATE: sharded handle, hard constraints; GSX_E_INDETERMINATE: the undamped
+ * system cannot be factored; GSX_E_NOMEM: the covariance arena (one (n - 1) x (n + F - 1) block per clique that is not
+ * a leaf-kernel clique, about the size of the front arena) does not fit; GSX_E_NO_DEVICE without a GPU. */
+int64_t    gsx_marginal_blocks_size(gsx_handle h, const uint64_t* keys, int32_t n_keys);
+gsx_status gsx_marginal_covariances(gsx_handle h, const uint64_t* keys, int32_t n_keys, double* out, int64_t n_out);
 
 /* ---- partial relinearization / re-elimination on a fixed graph (first step) ----------------------
  * The numeric core of an iSAM2 update (gtsam/nonlinear/ISAM2.cpp:419-484: relinearize the factors of the variables
