@@ -312,4 +312,73 @@ __device__ inline void bearing_range_2d(const double* pose, const double* pt, do
 }
 __device__ inline double wrap_angle(double a) { return atan2(sin(a), cos(a)); }
 
+// ---- Pose2::range (gtsam/geometry/Pose2.cpp:271-310) with norm2's derivative (Point2.cpp:27-36: d / r, or the row of
+// ones at r <= 1e-10).  pose = (x, y, theta), pt = the point or the other pose's translation; H1 1x3 (this pose) / Dd 1x2
+// (D range / D d, d in the world frame: the point's Jacobian; for a second pose multiply by its [R 0], :302-308).
+__device__ inline double range_2d(const double* pose, const double* pt, double* H1, double* Dd) {
+  const double dx = pt[0] - pose[0], dy = pt[1] - pose[1];
+  const double r = sqrt(dx * dx + dy * dy);
+  if (H1) {
+    const bool far = fabs(r) > 1e-10;
+    const double rx = far ? dx / r : 1.0, ry = far ? dy / r : 1.0;
+    const double c = cos(pose[2]), s = sin(pose[2]);
+    H1[0] = -rx * c - ry * s; H1[1] = rx * s - ry * c; H1[2] = 0.0;
+    Dd[0] = rx; Dd[1] = ry;
+  }
+  return r;
+}
+
+// ---- Pose3::range (gtsam/geometry/Pose3.cpp:408-431) = norm3 (Point3.cpp:41-50, the 1e-10 guard included) of
+// Pose3::transformTo (:380-397).  pose = R9 t3, pt = the point or the other pose's translation; H1 1x6 (this pose) / H2 1x3
+// (the point's Jacobian D_r_local R'; for a second pose [0 0 0, H2 R_other], :425-431).
+__device__ inline double range_3d(const double* pose, const double* pt, double* H1, double* H2) {
+  const double dx = pt[0] - pose[9], dy = pt[1] - pose[10], dz = pt[2] - pose[11];
+  const double qx = pose[0] * dx + pose[3] * dy + pose[6] * dz;
+  const double qy = pose[1] * dx + pose[4] * dy + pose[7] * dz;
+  const double qz = pose[2] * dx + pose[5] * dy + pose[8] * dz;
+  const double r = sqrt(qx * qx + qy * qy + qz * qz);
+  if (H1) {
+    const bool far = fabs(r) > 1e-10;
+    const double lx = far ? qx / r : 1.0, ly = far ? qy / r : 1.0, lz = far ? qz / r : 1.0;
+    // D_r_local [ [q]x  -I ]
+    H1[0] = ly * qz - lz * qy; H1[1] = lz * qx - lx * qz; H1[2] = lx * qy - ly * qx;
+    H1[3] = -lx; H1[4] = -ly; H1[5] = -lz;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) H2[j] = lx * pose[3 * j] + ly * pose[3 * j + 1] + lz * pose[3 * j + 2];
+  }
+  return r;
+}
+
+// ---- StereoCamera::project2 (gtsam/geometry/StereoCamera.cpp:37-79; returns false on cheirality, z <= 0) ------------
+// pose: R9 t3; K = (fx, fy, s, u0, v0, b) — the skew is not used, as in the reference.  out = (uL, uR, v);
+// H1 3x6 / H2 3x3 row-major when non-null.
+__device__ inline bool stereo_project(const double* pose, const double* pt, const double* K, double* out, double* H1,
+                                      double* H2) {
+  const double dx = pt[0] - pose[9], dy = pt[1] - pose[10], dz = pt[2] - pose[11];
+  const double x = pose[0] * dx + pose[3] * dy + pose[6] * dz;
+  const double y = pose[1] * dx + pose[4] * dy + pose[7] * dz;
+  const double z = pose[2] * dx + pose[5] * dy + pose[8] * dz;
+  if (z <= 0) return false;
+  const double fx = K[0], fy = K[1], b = K[5];
+  const double d = 1.0 / z;
+  const double dfx = d * fx, dfy = d * fy;
+  const double uL = dfx * x, uR = dfx * (x - b), v = dfy * y;
+  out[0] = K[3] + uL;
+  out[1] = K[3] + uR;
+  out[2] = K[4] + v;
+  if (H1) {
+    const double v1 = v / fy, v2 = fx * v1, dxx = d * x;
+    H1[0] = uL * v1; H1[1] = -fx - dxx * uL; H1[2] = v2; H1[3] = -dfx; H1[4] = 0.0; H1[5] = d * uL;
+    H1[6] = uR * v1; H1[7] = -fx - dxx * uR; H1[8] = v2; H1[9] = -dfx; H1[10] = 0.0; H1[11] = d * uR;
+    H1[12] = fy + v * v1; H1[13] = -dxx * v; H1[14] = -x * dfy; H1[15] = 0.0; H1[16] = -dfy; H1[17] = d * v;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      H2[j] = d * (fx * pose[3 * j] - pose[3 * j + 2] * uL);
+      H2[3 + j] = d * (fx * pose[3 * j] - pose[3 * j + 2] * uR);
+      H2[6 + j] = d * (fy * pose[3 * j + 1] - pose[3 * j + 2] * v);
+    }
+  }
+  return true;
+}
+
 }  // namespace gsxd

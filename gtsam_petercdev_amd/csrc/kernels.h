@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/gsx.h"
+
 namespace gsx {
 
 typedef long long i64;
@@ -158,11 +160,32 @@ void launch_cond_check(int n, const i64* last, const i64* prev, const int* front
 __host__ __device__ inline i64 big_panel_offset(int n) { return ((i64)n * n + 1) & ~(i64)1; }
 
 // ---- launches (all asynchronous on `st`) ---------------------------------------------------------
-void launch_linearize(const DevProblem& P, const int* const type_lists[6], const int type_counts[6],
+// The factor lists of the linearize / error kernels: one per factor family whose kernel knows its shapes at compile time
+// (a RangeFactor variant is a family), TL_GENERIC for the rare runtime-dimension ones.  GSX_F_LINEAR is in none.
+enum { TL_SFM = 0, TL_BETWEEN_POSE2 = 1, TL_BETWEEN_POSE3 = 2, TL_GENERIC = 3, TL_PROJECTION = 4, TL_BEARINGRANGE = 5,
+       TL_RANGE_POSE2_POINT = 6, TL_RANGE_POSE2_POSE = 7, TL_RANGE_POSE3_POINT = 8, TL_RANGE_POSE3_POSE = 9,
+       TL_BEARING = 10, TL_STEREO = 11, kNumTypeLists = 12 };
+// list of a factor of type `t` whose first two variables have types vt0, vt1 (-1: GSX_F_LINEAR, no list)
+inline int type_list_of(int t, int vt0, int vt1) {
+  switch (t) {
+    case GSX_F_LINEAR: return -1;
+    case GSX_F_SFM: return TL_SFM;
+    case GSX_F_PROJECTION: return TL_PROJECTION;
+    case GSX_F_BEARINGRANGE: return TL_BEARINGRANGE;
+    case GSX_F_BETWEEN: return vt0 == GSX_VAR_POSE2 ? TL_BETWEEN_POSE2 : (vt0 == GSX_VAR_POSE3 ? TL_BETWEEN_POSE3 : TL_GENERIC);
+    case GSX_F_RANGE:
+      return vt0 == GSX_VAR_POSE2 ? (vt1 == GSX_VAR_POSE2 ? TL_RANGE_POSE2_POSE : TL_RANGE_POSE2_POINT)
+                                  : (vt1 == GSX_VAR_POSE3 ? TL_RANGE_POSE3_POSE : TL_RANGE_POSE3_POINT);
+    case GSX_F_BEARING: return TL_BEARING;
+    case GSX_F_STEREO: return TL_STEREO;
+  }
+  return TL_GENERIC;
+}
+void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
                       const double* values, double* jac, DevStatus* status, hipStream_t st);
 // the graph error over the type lists of launch_linearize (a kernel per list, the factor type a compile-time constant)
-void launch_error(const DevProblem& P, const int* const type_lists[6], const int type_counts[6], const double* values,
-                  double* partials, int n_partials_cap, double* scalars, int slot, hipStream_t st);
+void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
+                  const double* values, double* partials, int n_partials_cap, double* scalars, int slot, hipStream_t st);
 // slice > 0: the staged kernel (doubles of LDS per wave = the largest [A b] range of 64 consecutive factors); 0: the direct one
 void launch_linear_error(const DevProblem& P, const double* jac, const double* delta, double* partials,
                          int n_partials_cap, double* scalars, int slice, hipStream_t st);

@@ -426,7 +426,103 @@ __global__ void linearize_generic_kernel(DevProblem P, const int* list, int n, c
   linearize_generic_body(P, list, n, values, jac, blockIdx.x);
 }
 
-void launch_linearize(const DevProblem& P, const int* const type_lists[6], const int type_counts[6],
+// RangeFactor<A1,A2> — gtsam/sam/RangeFactor.h (ExpressionFactor: e = range(a1, a2) - z, b = -e); V1 = POSE2 | POSE3,
+// V2 = VECTOR (a point of the pose's space) or V1 (a second pose: the range to its translation).  One row:
+// [A b] is 1 x (d1 + d2 + 1).
+template <int V1, int V2>
+__global__ void __launch_bounds__(256) linearize_range_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                              double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+  const double* a1 = values + fr.s0;
+  const double* a2 = values + fr.s1;
+  const double z = P.meas[fr.meas_off];
+  if constexpr (V1 == GSX_VAR_POSE2) {
+    constexpr int NC = (V2 == GSX_VAR_POSE2) ? 7 : 6;
+    double ps[3] = {a1[0], a1[1], a1[2]}, p2[2] = {a2[0], a2[1]}, H1[3], Dd[2], J[NC];
+    const double r = range_2d(ps, p2, H1, Dd);
+    J[0] = H1[0]; J[1] = H1[1]; J[2] = H1[2];
+    if constexpr (V2 == GSX_VAR_POSE2) {  // D d / D other = [R_other 0] (Pose2.cpp:302-308)
+      const double c2 = cos(a2[2]), s2 = sin(a2[2]);
+      J[3] = Dd[0] * c2 + Dd[1] * s2; J[4] = -Dd[0] * s2 + Dd[1] * c2; J[5] = 0.0;
+    } else {
+      J[3] = Dd[0]; J[4] = Dd[1];
+    }
+    J[NC - 1] = -(r - z);
+    whiten_store<1, NC>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+  } else {
+    constexpr int NC = (V2 == GSX_VAR_POSE3) ? 13 : 10;
+    constexpr int TO = (V2 == GSX_VAR_POSE3) ? 9 : 0;  // where the other variable's translation sits in its state
+    double pr[12], p3[3] = {a2[TO], a2[TO + 1], a2[TO + 2]}, H1[6], H2[3], J[NC];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pr[k] = a1[k];
+    const double r = range_3d(pr, p3, H1, H2);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) J[c] = H1[c];
+    if constexpr (V2 == GSX_VAR_POSE3) {  // [0 0 0, D_local_point R_other] (Pose3.cpp:425-431)
+      J[6] = J[7] = J[8] = 0.0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) J[9 + c] = H2[0] * a2[c] + H2[1] * a2[3 + c] + H2[2] * a2[6 + c];
+    } else {
+      J[6] = H2[0]; J[7] = H2[1]; J[8] = H2[2];
+    }
+    J[NC - 1] = -(r - z);
+    whiten_store<1, NC>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+  }
+}
+
+// BearingFactor<Pose2,Point2> — gtsam/sam/BearingFactor.h: the bearing row of BearingRangeFactor
+__global__ void __launch_bounds__(256) linearize_bearing_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+  const double* pose = values + fr.s0;
+  const double* pt = values + fr.s1;
+  double ps[3] = {pose[0], pose[1], pose[2]}, p2[2] = {pt[0], pt[1]}, br[2], H1[6], H2[4], J[6];
+  bearing_range_2d(ps, p2, br, H1, H2);
+  J[0] = H1[0]; J[1] = H1[1]; J[2] = H1[2];
+  J[3] = H2[0]; J[4] = H2[1];
+  J[5] = -wrap_angle(br[0] - P.meas[fr.meas_off]);
+  whiten_store<1, 6>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+
+// GenericStereoFactor<Pose3,Point3>::evaluateError — gtsam/slam/StereoFactor.h:126-154
+__global__ void __launch_bounds__(256) linearize_stereo_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                               double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+  const double* pose = values + fr.s0;
+  const double* pt = values + fr.s1;
+  const double* z = P.meas + fr.meas_off;  // uL uR v fx fy s u0 v0 b
+  double pr[12], p3[3], K[6], pi[3], H1[18], H2[9], J[30];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) pr[k] = pose[k];
+  p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) K[k] = z[3 + k];
+  if (stereo_project(pr, p3, K, pi, H1, H2)) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) J[3 * c + r] = H1[6 * r + c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) J[18 + 3 * c + r] = H2[3 * r + c];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) J[27 + r] = z[r] - pi[r];  // b = -(h(x) - z)
+  } else {  // point behind the camera: zero Jacobians, error (2 fx, 2 fx, 2 fx)
+#pragma unroll
+    for (int k = 0; k < 27; ++k) J[k] = 0;
+    J[27] = J[28] = J[29] = -2.0 * K[0];
+  }
+  whiten_store<3, 10>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+
+void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
                       const double* values, double* jac, DevStatus* status, hipStream_t st) {
   auto grid = [](int n) { return dim3((n + 255) / 256); };
   // the generic family (priors, vector-space factors: few) rides in the first blocks of the first main family's launch
@@ -454,6 +550,15 @@ void launch_linearize(const DevProblem& P, const int* const type_lists[6], const
     linearize_projection_kernel<<<grid(type_counts[4]), 256, 0, st>>>(P, type_lists[4], type_counts[4], values, jac);
   if (type_counts[5])
     linearize_bearingrange_kernel<<<grid(type_counts[5]), 256, 0, st>>>(P, type_lists[5], type_counts[5], values, jac);
+  auto run = [&](auto kernel, int k) {
+    if (type_counts[k]) kernel<<<grid(type_counts[k]), 256, 0, st>>>(P, type_lists[k], type_counts[k], values, jac);
+  };
+  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_VECTOR>, TL_RANGE_POSE2_POINT);
+  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_POSE2>, TL_RANGE_POSE2_POSE);
+  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR>, TL_RANGE_POSE3_POINT);
+  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3>, TL_RANGE_POSE3_POSE);
+  run(linearize_bearing_kernel, TL_BEARING);
+  run(linearize_stereo_kernel, TL_STEREO);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -506,6 +611,48 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
       e[0] = e[1] = 2.0 * K[0];
     }
     return whitened_half_sqnorm<2>(e, kind, np);
+  }
+  // the families below have kernels of their own only (launch_error): compiled out of the <-1, -1> form
+  if constexpr (FT == GSX_F_RANGE && FV == GSX_VAR_POSE2) {
+    const double* a1 = values + fr.s0;
+    const double* a2 = values + fr.s1;  // a point, or a pose whose translation comes first
+    double ps[3] = {a1[0], a1[1], a1[2]}, p2[2] = {a2[0], a2[1]}, e[1];
+    e[0] = range_2d(ps, p2, nullptr, nullptr) - z[0];
+    return whitened_half_sqnorm<1>(e, kind, np);
+  }
+  if constexpr (FT == GSX_F_RANGE && FV == GSX_VAR_POSE3) {
+    const double* a1 = values + fr.s0;
+    const double* a2 = values + fr.s1 + ((fr.rows_dim >> 16) == 13 ? 9 : 0);  // 13 columns: the other is a pose (R9 t3)
+    double pr[12], p3[3] = {a2[0], a2[1], a2[2]}, e[1];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pr[k] = a1[k];
+    e[0] = range_3d(pr, p3, nullptr, nullptr) - z[0];
+    return whitened_half_sqnorm<1>(e, kind, np);
+  }
+  if constexpr (FT == GSX_F_BEARING) {
+    const double* pose = values + fr.s0;
+    const double* pt = values + fr.s1;
+    double ps[3] = {pose[0], pose[1], pose[2]}, p2[2] = {pt[0], pt[1]}, br[2], e[1];
+    bearing_range_2d(ps, p2, br, nullptr, nullptr);
+    e[0] = wrap_angle(br[0] - z[0]);
+    return whitened_half_sqnorm<1>(e, kind, np);
+  }
+  if constexpr (FT == GSX_F_STEREO) {
+    const double* pose = values + fr.s0;
+    const double* pt = values + fr.s1;
+    double pr[12], p3[3], K[6], pi[3], e[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pr[k] = pose[k];
+    p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) K[k] = z[3 + k];
+    if (stereo_project(pr, p3, K, pi, nullptr, nullptr)) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) e[r] = pi[r] - z[r];
+    } else {
+      e[0] = e[1] = e[2] = 2.0 * K[0];
+    }
+    return whitened_half_sqnorm<3>(e, kind, np);
   }
   const int vt = FV >= 0 ? FV : ((fr.type_kind >> 24) & 0xff);
   if (type == GSX_F_BETWEEN && vt == GSX_VAR_POSE2) {
@@ -575,18 +722,19 @@ __global__ void __launch_bounds__(256) error_list_kernel(DevProblem P, const int
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-void launch_error(const DevProblem& P, const int* const type_lists[6], const int type_counts[6], const double* values,
-                  double* partials, int cap, double* scalars, int slot, hipStream_t st) {
+void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists],
+                  const int type_counts[kNumTypeLists], const double* values, double* partials, int cap, double* scalars,
+                  int slot, hipStream_t st) {
   // a launch per non-empty list, its blocks a share of the partial sums proportional to its factors; the sums are added in
   // list order, block order: deterministic
   long long total = 0;
-  for (int k = 0; k < 6; ++k) total += type_counts[k];
+  for (int k = 0; k < kNumTypeLists; ++k) total += type_counts[k];
   int off = 0;
-  for (int k = 0; k < 6; ++k) {
+  for (int k = 0; k < kNumTypeLists; ++k) {
     const int n = type_counts[k];
     if (!n) continue;
     int nb = (n + 255) / 256;
-    const int share = (int)std::max<long long>(1, (long long)(cap - 6) * n / std::max<long long>(total, 1));
+    const int share = (int)std::max<long long>(1, (long long)(cap - kNumTypeLists) * n / std::max<long long>(total, 1));
     nb = std::min(nb, share);
     double* out = partials + off;
     switch (k) {
@@ -595,6 +743,12 @@ void launch_error(const DevProblem& P, const int* const type_lists[6], const int
       case 2: error_list_kernel<GSX_F_BETWEEN, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case 4: error_list_kernel<GSX_F_PROJECTION, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case 5: error_list_kernel<GSX_F_BEARINGRANGE, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_RANGE_POSE2_POINT:
+      case TL_RANGE_POSE2_POSE: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_RANGE_POSE3_POINT:
+      case TL_RANGE_POSE3_POSE: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_BEARING: error_list_kernel<GSX_F_BEARING, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_STEREO: error_list_kernel<GSX_F_STEREO, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       default: error_list_kernel<-1, -1><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
     }
     off += nb;

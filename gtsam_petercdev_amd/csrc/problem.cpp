@@ -105,6 +105,17 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
       case GSX_F_PROJECTION:
         ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && m == 2 && nmeas == 7;
         break;
+      case GSX_F_RANGE:  // (POSE2 | POSE3) to a point of its space or to a pose of its kind
+        ok = ok && nk == 2 && (tv(0) == GSX_VAR_POSE2 || tv(0) == GSX_VAR_POSE3) &&
+             (tv(1) == tv(0) || (tv(1) == GSX_VAR_VECTOR && dv(1) == (tv(0) == GSX_VAR_POSE2 ? 2 : 3))) && m == 1 &&
+             nmeas == 1;
+        break;
+      case GSX_F_BEARING:
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE2 && tv(1) == GSX_VAR_VECTOR && dv(1) == 2 && m == 1 && nmeas == 1;
+        break;
+      case GSX_F_STEREO:
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && m == 3 && nmeas == 9;
+        break;
       default:
         ok = false;
     }

@@ -117,8 +117,8 @@ struct gsx_context {
   DevBuf<i64> d_f_meas_off, d_f_noise_off, d_f_jac_off;
   DevBuf<double> d_meas, d_noise;
   DevBuf<FactorRec> d_frec;
-  DevBuf<int> d_type_list[6];
-  int type_count[6] = {0, 0, 0, 0, 0, 0};
+  DevBuf<int> d_type_list[kNumTypeLists];
+  int type_count[kNumTypeLists] = {};
   DevProblem DP{};
   // device symbolic
   DevBuf<i64> d_fr_off, d_cmap_ptr, d_gidx_ptr, d_h_off, d_hmap_ptr, d_term_ptr;
@@ -271,7 +271,7 @@ struct gsx_context {
   std::vector<int> fr_seg_ptr, fr_segs, seg_level; // destination front -> its gather segments; segment -> gather group
   std::vector<int> fr_gm_ptr, fr_gms, gm_level;    // ... and its multi-segment combine entries
   struct PartialScratch {                          // device tables of gsx_relinearize_partial, reused between calls
-    DevBuf<int> marked, src_off, lists[6], hv, ids, gm_task, gm_slot, gm_nslots;
+    DevBuf<int> marked, src_off, lists[kNumTypeLists], hv, ids, gm_task, gm_slot, gm_nslots;
     DevBuf<double> states;
     DevBuf<LeafRec> leaf;
     DevBuf<BigDesc> big;
@@ -355,25 +355,24 @@ void timers_resolve(gsx_context* c) {
   }
 }
 
+// the list of factor f (kernels.h: type_list_of; the types of its first two variables pick the family's variant)
+static int factor_type_list(const HostProblem& P, int f) {
+  const int kp = P.f_key_ptr[f], nk = P.f_key_ptr[f + 1] - kp;
+  return type_list_of(P.f_type[f], nk > 0 ? P.types[P.f_vars[kp]] : -1, nk > 1 ? P.types[P.f_vars[kp + 1]] : -1);
+}
 // factor lists of the linearize kernels (one per factor family) and of the error kernels; `owned` (may be null: all)
 // restricts them to the factors this rank evaluates
 gsx_status upload_factor_lists(gsx_context* c, const std::vector<char>* owned) {
   const HostProblem& P = c->P;
   hipStream_t st = c->stream;
-  std::vector<int> lists[6], active;
+  std::vector<int> lists[kNumTypeLists], active;
   for (int f = 0; f < P.n_factors; ++f) {
     if (owned && !(*owned)[f]) continue;
     active.push_back(f);
-    const int t = P.f_type[f];
-    const int vt = P.types[P.f_vars[P.f_key_ptr[f]]];
-    if (t == GSX_F_SFM) lists[0].push_back(f);
-    else if (t == GSX_F_PROJECTION) lists[4].push_back(f);
-    else if (t == GSX_F_BEARINGRANGE) lists[5].push_back(f);
-    else if (t == GSX_F_BETWEEN && vt == GSX_VAR_POSE2) lists[1].push_back(f);
-    else if (t == GSX_F_BETWEEN && vt == GSX_VAR_POSE3) lists[2].push_back(f);
-    else if (t != GSX_F_LINEAR) lists[3].push_back(f);
+    const int k = factor_type_list(P, f);
+    if (k >= 0) lists[k].push_back(f);
   }
-  for (int k = 0; k < 6; ++k) {
+  for (int k = 0; k < kNumTypeLists; ++k) {
     c->type_count[k] = (int)lists[k].size();
     HIPCHK(c, c->d_type_list[k].upload(lists[k], st));
   }
@@ -1212,8 +1211,8 @@ void shard_allreduce(gsx_context* c, double* dptr, int64_t n) {
 void dev_linearize(gsx_context* c) {
   timer_begin(c, PH_LINEARIZE);
   hipMemsetAsync(&c->d_status.p->n_cheirality, 0, sizeof(int), c->stream);
-  const int* lists[6] = {c->d_type_list[0].p, c->d_type_list[1].p, c->d_type_list[2].p, c->d_type_list[3].p,
-                         c->d_type_list[4].p, c->d_type_list[5].p};
+  const int* lists[kNumTypeLists];
+  for (int k = 0; k < kNumTypeLists; ++k) lists[k] = c->d_type_list[k].p;
   launch_linearize(c->DP, lists, c->type_count, c->d_values.p, c->d_jac.p, c->d_status.p, c->stream);
   timer_end(c, PH_LINEARIZE);
   c->sc_dirty |= kXLin;
@@ -1648,8 +1647,8 @@ void dev_retract(gsx_context* c, const double* d_delta) {
 }
 void dev_error(gsx_context* c, const double* d_vals, int slot) {
   timer_begin(c, PH_ERROR);
-  const int* lists[6] = {c->d_type_list[0].p, c->d_type_list[1].p, c->d_type_list[2].p, c->d_type_list[3].p,
-                         c->d_type_list[4].p, c->d_type_list[5].p};
+  const int* lists[kNumTypeLists];
+  for (int k = 0; k < kNumTypeLists; ++k) lists[k] = c->d_type_list[k].p;
   launch_error(c->DP, lists, c->type_count, d_vals, c->d_partials.p, gsx_context::kPartials, c->d_scalars.p, slot, c->stream);
   c->sc_dirty |= 1u << slot;
   timer_end(c, PH_ERROR);
@@ -2561,20 +2560,14 @@ gsx_status partial_linearize(gsx_handle h, std::vector<int>& dfac) {
   gsx_context::PartialScratch& ps = h->ps;
   {
     std::sort(dfac.begin(), dfac.end());
-    std::vector<int> lists[6];
+    std::vector<int> lists[kNumTypeLists];
     for (int f : dfac) {
-      const int t = P.f_type[f];
-      const int vt = P.types[P.f_vars[P.f_key_ptr[f]]];
-      if (t == GSX_F_SFM) lists[0].push_back(f);
-      else if (t == GSX_F_PROJECTION) lists[4].push_back(f);
-      else if (t == GSX_F_BEARINGRANGE) lists[5].push_back(f);
-      else if (t == GSX_F_BETWEEN && vt == GSX_VAR_POSE2) lists[1].push_back(f);
-      else if (t == GSX_F_BETWEEN && vt == GSX_VAR_POSE3) lists[2].push_back(f);
-      else if (t != GSX_F_LINEAR) lists[3].push_back(f);
+      const int k = factor_type_list(P, f);
+      if (k >= 0) lists[k].push_back(f);
     }
-    const int* lp[6];
-    int cnt[6];
-    for (int k = 0; k < 6; ++k) {
+    const int* lp[kNumTypeLists];
+    int cnt[kNumTypeLists];
+    for (int k = 0; k < kNumTypeLists; ++k) {
       HIPCHK(h, ps.lists[k].stage(lists[k], sm));
       lp[k] = ps.lists[k].p;
       cnt[k] = (int)lists[k].size();

@@ -169,6 +169,14 @@ class Pose3:
     def between(self, o):
         return self.inverse().compose(o)
 
+    def transformFrom(self, point):
+        """Pose3::transformFrom (gtsam/geometry/Pose3.cpp:356-369): R p + t."""
+        return self.R_.R @ np.asarray(point, dtype=float).reshape(3) + self.t_
+
+    def transformTo(self, point):
+        """Pose3::transformTo (gtsam/geometry/Pose3.cpp:380-397): R' (p - t)."""
+        return self.R_.R.T @ (np.asarray(point, dtype=float).reshape(3) - self.t_)
+
     def equals(self, o, tol=1e-9):
         return np.allclose(self.R_.R, o.R_.R, atol=tol) and np.allclose(self.t_, o.t_, atol=tol)
 
@@ -441,6 +449,70 @@ def BearingRangeFactor(poseKey, pointKey, bearing, range_, model):
 BearingRangeFactor2D = BearingRangeFactor
 
 
+def BearingFactor(poseKey, pointKey, measured, model):
+    """BearingFactor<Pose2, Point2>(poseKey, pointKey, Rot2 measured, model) — gtsam/sam/BearingFactor.h; `measured` is
+    the angle in radians (Rot2::fromAngle)."""
+    return _Factor(A.F_BEARING, [poseKey, pointKey], 1, [float(measured)], model)
+
+
+BearingFactor2D = BearingFactor
+
+
+def RangeFactor(key1, key2, measured, model):
+    """RangeFactor<A1, A2>(key1, key2, measured, model) — gtsam/sam/RangeFactor.h.  The variant — (Pose2, Point2),
+    (Pose2, Pose2), (Pose3, Point3) or (Pose3, Pose3) — is the one of the two variables in the Values the graph is lowered
+    with; any other pair is refused there (NonlinearFactorGraph.to_arrays)."""
+    return _Factor(A.F_RANGE, [key1, key2], 1, [float(measured)], model)
+
+
+RangeFactor2D = RangeFactorPose2 = RangeFactor3D = RangeFactorPose3 = RangeFactor
+
+
+class Cal3_S2Stereo:
+    """gtsam/geometry/Cal3_S2Stereo.h: (fx, fy, s, u0, v0, b)."""
+
+    def __init__(self, fx=1.0, fy=1.0, s=0.0, u0=0.0, v0=0.0, b=1.0):
+        self.v = np.array([fx, fy, s, u0, v0, b], dtype=float)
+
+    def fx(self):
+        return float(self.v[0])
+
+    def baseline(self):
+        return float(self.v[5])
+
+    def vector(self):
+        return self.v.copy()
+
+
+class StereoPoint2:
+    """gtsam/geometry/StereoPoint2.h: (uL, uR, v)."""
+
+    def __init__(self, uL=0.0, uR=0.0, v=0.0):
+        self.v_ = np.array([uL, uR, v], dtype=float)
+
+    def uL(self):
+        return float(self.v_[0])
+
+    def uR(self):
+        return float(self.v_[1])
+
+    def v(self):
+        return float(self.v_[2])
+
+    def vector(self):
+        return self.v_.copy()
+
+
+def GenericStereoFactor(measured, model, poseKey, landmarkKey, K: "Cal3_S2Stereo"):
+    """GenericStereoFactor<Pose3, Point3>(measured, model, poseKey, landmarkKey, K) — gtsam/slam/StereoFactor.h (no
+    body_P_sensor, default cheirality flags)."""
+    z = measured.vector() if isinstance(measured, StereoPoint2) else np.asarray(measured, dtype=float).reshape(3)
+    return _Factor(A.F_STEREO, [poseKey, landmarkKey], 3, np.concatenate([z, K.vector()]), model)
+
+
+GenericStereoFactor3D = GenericStereoFactor
+
+
 def JacobianFactor(*args):
     """JacobianFactor(key1, A1, [key2, A2, ...], b[, model]) — gtsam/linear/JacobianFactor.h.
     A diagonal/isotropic model is folded in by the backend (whitening)."""
@@ -554,6 +626,12 @@ class NonlinearFactorGraph:
                 if k not in index:
                     raise KeyError(f"ValuesKeyDoesNotExist: {k}")
                 fvars.append(index[k])
+            if f.ftype == A.F_RANGE and values is not None:  # the variant is the one of the two variables' types
+                (t1, d1), (t2, d2) = [(types[index[k]], dims[index[k]]) for k in f.keys_]
+                if t1 not in (A.VAR_POSE2, A.VAR_POSE3) or not (
+                        t2 == t1 or (t2 == A.VAR_VECTOR and d2 == (2 if t1 == A.VAR_POSE2 else 3))):
+                    raise ValueError(f"RangeFactor between variables {f.keys_}: not (Pose2 | Pose3) to a point of its space "
+                                     "or to a pose of its kind")
             key_ptr.append(len(fvars))
             meas.append(f.meas)
             meas_ptr.append(meas_ptr[-1] + f.meas.size)

@@ -107,12 +107,36 @@ enum {
                                VECTOR(3)); meas = (u, v, fx, fy, s, u0, v0).
                                Cheirality (default flags): zero Jacobians and the
                                constant error (2 fx, 2 fx)                         */
-  GSX_F_BEARINGRANGE = 5    /* BearingRangeFactor<Pose2,Point2> (gtsam/sam/
+  GSX_F_BEARINGRANGE = 5,   /* BearingRangeFactor<Pose2,Point2> (gtsam/sam/
                                BearingRangeFactor.h; Pose2::bearing / range,
                                gtsam/geometry/Pose2.cpp:246-285, Rot2.cpp:119-130);
                                keys (POSE2, VECTOR(2)); meas = (bearing angle,
                                range); error = (wrapped bearing difference,
                                range difference)                                   */
+  GSX_F_RANGE = 6,          /* RangeFactor<A1,A2> (gtsam/sam/RangeFactor.h); keys
+                               (POSE2, VECTOR(2)), (POSE2, POSE2), (POSE3, VECTOR(3))
+                               or (POSE3, POSE3); m = 1; meas = (range); error =
+                               range(a1, a2) - z.  Pose2::range (gtsam/geometry/
+                               Pose2.cpp:271-310), Pose3::range (Pose3.cpp:408-431).
+                               At a distance <= 1e-10 the derivative of the norm is
+                               the row of ones norm2 / norm3 hand out there
+                               (Point2.cpp:27-36, Point3.cpp:41-50), not a division
+                               by zero                                             */
+  GSX_F_BEARING = 7,        /* BearingFactor<Pose2,Point2> (gtsam/sam/BearingFactor.h;
+                               Pose2::bearing, Pose2.cpp:246-257); keys (POSE2,
+                               VECTOR(2)); m = 1; meas = (bearing angle); error = the
+                               wrapped bearing difference: the first row of
+                               GSX_F_BEARINGRANGE                                  */
+  GSX_F_STEREO = 8          /* GenericStereoFactor<Pose3,Point3> (gtsam/slam/
+                               StereoFactor.h:126-154) with a fixed Cal3_S2Stereo and
+                               no body_P_sensor; keys (POSE3, VECTOR(3)); m = 3; meas =
+                               (uL, uR, v, fx, fy, s, u0, v0, b).  StereoCamera::
+                               project2 (gtsam/geometry/StereoCamera.cpp:37-79): uL =
+                               u0 + fx x/z, uR = u0 + fx (x - b)/z, v = v0 + fy y/z —
+                               the skew s is carried but, as there, not used.
+                               Cheirality (default flags): z <= 0 in the camera frame
+                               gives zero Jacobians and the constant error
+                               (2 fx, 2 fx, 2 fx)                                  */
 };
 
 /* ---- noise model kinds (gtsam/linear/NoiseModel.cpp) --------------------- */

@@ -23,6 +23,7 @@
 
 #include <gtsam/geometry/Cal3Bundler.h>
 #include <gtsam/geometry/Cal3_S2.h>
+#include <gtsam/geometry/Cal3_S2Stereo.h>
 #include <gtsam/geometry/PinholeCamera.h>
 #include <gtsam/geometry/Pose2.h>
 #include <gtsam/geometry/Pose3.h>
@@ -34,10 +35,13 @@
 #include <gtsam/nonlinear/LevenbergMarquardtOptimizer.h>
 #include <gtsam/nonlinear/PriorFactor.h>
 #include <gtsam/nonlinear/internal/LevenbergMarquardtState.h>
+#include <gtsam/sam/BearingFactor.h>
 #include <gtsam/sam/BearingRangeFactor.h>
+#include <gtsam/sam/RangeFactor.h>
 #include <gtsam/slam/BetweenFactor.h>
 #include <gtsam/slam/GeneralSFMFactor.h>
 #include <gtsam/slam/ProjectionFactor.h>
+#include <gtsam/slam/StereoFactor.h>
 
 #include <map>
 #include <numeric>
@@ -156,12 +160,16 @@ inline bool lower_factor(const gtsam::NonlinearFactor::shared_ptr& f, Lowered& L
     pack(b3->measured(), m), L.add_factor(GSX_F_BETWEEN, 6, ks, m, kind, np);
   } else if (auto bp = std::dynamic_pointer_cast<BetweenFactor<Point3>>(f)) {
     pack(Vector(bp->measured()), m), L.add_factor(GSX_F_BETWEEN, 3, ks, m, kind, np);
+  } else if (auto bq = std::dynamic_pointer_cast<BetweenFactor<Point2>>(f)) {
+    pack(Vector(bq->measured()), m), L.add_factor(GSX_F_BETWEEN, 2, ks, m, kind, np);
   } else if (auto p2 = std::dynamic_pointer_cast<PriorFactor<Pose2>>(f)) {
     pack(p2->prior(), m), L.add_factor(GSX_F_PRIOR, 3, ks, m, kind, np);
   } else if (auto p3 = std::dynamic_pointer_cast<PriorFactor<Pose3>>(f)) {
     pack(p3->prior(), m), L.add_factor(GSX_F_PRIOR, 6, ks, m, kind, np);
   } else if (auto pp = std::dynamic_pointer_cast<PriorFactor<Point3>>(f)) {
     pack(Vector(pp->prior()), m), L.add_factor(GSX_F_PRIOR, 3, ks, m, kind, np);
+  } else if (auto pq = std::dynamic_pointer_cast<PriorFactor<Point2>>(f)) {
+    pack(Vector(pq->prior()), m), L.add_factor(GSX_F_PRIOR, 2, ks, m, kind, np);
   } else if (auto pc = std::dynamic_pointer_cast<PriorFactor<PinholeCamera<Cal3Bundler>>>(f)) {
     pack(pc->prior(), m), L.add_factor(GSX_F_PRIOR, 9, ks, m, kind, np);
   } else if (auto pr = std::dynamic_pointer_cast<GenericProjectionFactor<Pose3, Point3, Cal3_S2>>(f)) {
@@ -171,6 +179,22 @@ inline bool lower_factor(const gtsam::NonlinearFactor::shared_ptr& f, Lowered& L
                  kind, np);
   } else if (auto br = std::dynamic_pointer_cast<BearingRangeFactor<Pose2, Point2>>(f)) {
     L.add_factor(GSX_F_BEARINGRANGE, 2, ks, {br->measured().bearing().theta(), br->measured().range()}, kind, np);
+  } else if (auto r2 = std::dynamic_pointer_cast<RangeFactor<Pose2, Point2>>(f)) {  // (the variant is the variables' types)
+    L.add_factor(GSX_F_RANGE, 1, ks, {r2->measured()}, kind, np);
+  } else if (auto r22 = std::dynamic_pointer_cast<RangeFactor<Pose2, Pose2>>(f)) {
+    L.add_factor(GSX_F_RANGE, 1, ks, {r22->measured()}, kind, np);
+  } else if (auto r3 = std::dynamic_pointer_cast<RangeFactor<Pose3, Point3>>(f)) {
+    L.add_factor(GSX_F_RANGE, 1, ks, {r3->measured()}, kind, np);
+  } else if (auto r33 = std::dynamic_pointer_cast<RangeFactor<Pose3, Pose3>>(f)) {
+    L.add_factor(GSX_F_RANGE, 1, ks, {r33->measured()}, kind, np);
+  } else if (auto bf = std::dynamic_pointer_cast<BearingFactor<Pose2, Point2>>(f)) {
+    L.add_factor(GSX_F_BEARING, 1, ks, {bf->measured().theta()}, kind, np);
+  } else if (auto sf = std::dynamic_pointer_cast<GenericStereoFactor<Pose3, Point3>>(f)) {
+    if (sf->body_P_sensor()) return false;
+    const Cal3_S2Stereo& K = *sf->calibration();
+    const StereoPoint2& z = sf->measured();
+    L.add_factor(GSX_F_STEREO, 3, ks, {z.uL(), z.uR(), z.v(), K.fx(), K.fy(), K.skew(), K.px(), K.py(), K.baseline()}, kind,
+                 np);
   } else {
     return false;
   }
