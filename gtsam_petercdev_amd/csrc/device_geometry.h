@@ -304,8 +304,10 @@ __device__ inline void bearing_range_2d(const double* pose, const double* pt, do
     // D q / D pose = [-1 0 qy; 0 -1 -qx], D q / D point = R'
     H1[0] = -bx; H1[1] = -by; H1[2] = bx * qy - by * qx;
     H2[0] = bx * c - by * s; H2[1] = bx * s + by * c;
-    // range: d = point - t (world), D r / D d = d' / r, D d / D pose = [-c s 0; -s -c 0]
-    const double rx = dx / n, ry = dy / n;
+    // range: d = point - t (world), D r / D d = d' / r — norm2's row of ones at r <= 1e-10 (Point2.cpp:27-36), not 0 / 0 —
+    // D d / D pose = [-c s 0; -s -c 0]
+    const bool apart = fabs(n) > 1e-10;
+    const double rx = apart ? dx / n : 1.0, ry = apart ? dy / n : 1.0;
     H1[3] = -rx * c - ry * s; H1[4] = rx * s - ry * c; H1[5] = 0.0;
     H2[2] = rx; H2[3] = ry;
   }

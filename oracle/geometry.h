@@ -344,7 +344,8 @@ inline void bearing_range_2d(const double* pose, const double* pt, double* br, d
     const double bx = far ? -qy / d2 : 0.0, by = far ? qx / d2 : 0.0;
     H1[0] = -bx; H1[1] = -by; H1[2] = bx * qy - by * qx;
     H2[0] = bx * c - by * s; H2[1] = bx * s + by * c;
-    const double rx = dx / n, ry = dy / n;
+    const bool apart = std::abs(n) > 1e-10;  // norm2's row of ones at r <= 1e-10 (Point2.cpp:27-36), not 0 / 0
+    const double rx = apart ? dx / n : 1.0, ry = apart ? dy / n : 1.0;
     H1[3] = -rx * c - ry * s; H1[4] = rx * s - ry * c; H1[5] = 0.0;
     H2[2] = rx; H2[3] = ry;
   }

@@ -18,20 +18,31 @@ def skew(w):
     return np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0.0]])
 
 
-def so3_expmap(w):
-    """SO3::Expmap (gtsam/geometry/SO3.cpp:61-96), near-zero branch by Taylor."""
+def so3_expmap(w, near_zero=False):
+    """SO3::Expmap = so3::ExpmapFunctor (gtsam/geometry/SO3.cpp:61-96): the second-order Taylor form when the caller says
+    so (Pose3::Expmap does, at w.w <= 1e-5) or at w.w <= epsilon (:62-63)."""
     th2 = float(w @ w)
     W = skew(w)
-    if th2 <= 1e-10:
-        return np.eye(3) + W + 0.5 * (W @ W)
+    if near_zero or th2 <= np.finfo(float).eps:
+        return np.eye(3) + (1.0 - th2 / 6.0) * W + (0.5 - th2 / 24.0) * (W @ W)
     th = math.sqrt(th2)
-    return np.eye(3) + (math.sin(th) / th) * W + ((1 - math.cos(th)) / th2) * (W @ W)
+    s2 = math.sin(th / 2.0)
+    return np.eye(3) + (math.sin(th) / th) * W + (2.0 * s2 * s2 / th2) * (W @ W)
 
 
 def so3_logmap(R):
-    """SO3::Logmap (gtsam/geometry/SO3.cpp:299-375) away from pi (the tests keep their rotations there)."""
-    tr = np.trace(R)
-    assert tr + 1.0 > 1e-3, "rotation too close to pi for this restatement"
+    """SO3::Logmap (gtsam/geometry/SO3.cpp:299-375), the near-pi branch (:316-356) included: with a the largest diagonal
+    entry and (a, b, c) cyclic, W = R_cb - R_bc, Q1 = 2 + 2 R_aa, Q2 = R_ab + R_ba, Q3 = R_ca + R_ac."""
+    tr = (R[0, 0] + R[1, 1]) + R[2, 2]
+    if tr + 1.0 < 1e-3:
+        a = 2 if (R[2, 2] > R[1, 1] and R[2, 2] > R[0, 0]) else (1 if R[1, 1] > R[0, 0] else 0)
+        b, c = (a + 1) % 3, (a + 2) % 3
+        W, Q1, Q2, Q3 = R[c, b] - R[b, c], 2.0 + 2.0 * R[a, a], R[a, b] + R[b, a], R[c, a] + R[a, c]
+        sgn = -1.0 if W < 0 else 1.0
+        mag = math.pi - (2 * sgn * W) / math.sqrt(Q1 * Q1 + Q2 * Q2 + Q3 * Q3 + W * W)
+        om = np.zeros(3)
+        om[[a, b, c]] = sgn * 0.5 / math.sqrt(Q1) * mag * np.array([Q1, Q2, Q3])
+        return om
     tr_3 = tr - 3.0
     if tr_3 < -1e-6:
         th = math.acos((tr - 1.0) / 2.0)
@@ -62,16 +73,21 @@ def pose3_logmap(R, t):
 
 
 def pose3_expmap(xi):
-    """Pose3::Expmap (gtsam/geometry/Pose3.cpp:184-222)."""
+    """Pose3::Expmap (gtsam/geometry/Pose3.cpp:184-222): nearZero = w.w <= 1e-5 (:189); t = v + B w x v + C w x (w x v)
+    (so3::DexpFunctor::applyLeftJacobian, SO3.cpp:165-174) with the second-order Taylor B, C there (:74, :107)."""
     w, v = xi[:3], xi[3:]
-    R = so3_expmap(w)
     th2 = float(w @ w)
-    if th2 <= 1e-10:
-        return R, v + 0.5 * np.cross(w, v)
-    th = math.sqrt(th2)
-    W = skew(w)
-    V = np.eye(3) + ((1 - math.cos(th)) / th2) * W + ((th - math.sin(th)) / (th2 * th)) * (W @ W)
-    return R, V @ v
+    near = th2 <= 1e-5
+    R = so3_expmap(w, near)
+    if near:
+        B, C = 0.5 - th2 / 24.0, 1.0 / 6.0 - th2 / 120.0
+    else:
+        th = math.sqrt(th2)
+        s2 = math.sin(th / 2.0)
+        B = 2.0 * s2 * s2 / th2
+        C = (1.0 - math.sin(th) / th) / th2
+    wv = np.cross(w, v)
+    return R, v + B * wv + C * np.cross(w, wv)
 
 
 def pose3_adjoint(R, t):
@@ -283,10 +299,10 @@ def whitener(arr, f):
     return W, loss, (p[nb] if loss else 0.0)
 
 
-def linearized(arr, values, f):
+def linearized(arr, values, f, evaluate=None):
     """The whitened m x (sum d + 1) block [A b] of factor f, Robust::WhitenSystem's reweighting included
     (gtsam/linear/NoiseModel.cpp:714-722), and whether the factor sat in its cheirality branch."""
-    e, Hs, cheir = evaluate(arr, values, f)
+    e, Hs, cheir = (evaluate or globals()["evaluate"])(arr, values, f)
     W, loss, k = whitener(arr, f)
     Ab = W @ np.hstack(Hs + [-e.reshape(-1, 1)])
     if loss:
@@ -294,35 +310,36 @@ def linearized(arr, values, f):
     return Ab, cheir
 
 
-def jacobians(arr, values):
+def jacobians(arr, values, evaluate=None):
     """What gsx_get_jacobians returns: every [A b], graph order, column-major; and the count of cheirality factors."""
     out, n_cheir = [], 0
     for f in range(arr.n_factors):
-        Ab, cheir = linearized(arr, values, f)
+        Ab, cheir = linearized(arr, values, f, evaluate)
         out.append(Ab.reshape(-1, order="F"))
         n_cheir += int(cheir)
     return np.concatenate(out), n_cheir
 
 
-def factor_error(arr, values, f):
+def factor_error(arr, values, f, evaluate=None):
     """NoiseModelFactor::error (gtsam/nonlinear/NonlinearFactor.cpp:138-149)."""
-    e, _, _ = evaluate(arr, values, f)
+    e, _, _ = (evaluate or globals()["evaluate"])(arr, values, f)
     W, loss, k = whitener(arr, f)
     d = float(np.linalg.norm(W @ e))
     return robust_loss(loss, k, d) if loss else 0.5 * d * d
 
 
-def graph_error(arr, values):
-    return math.fsum(factor_error(arr, values, f) for f in range(arr.n_factors))
+def graph_error(arr, values, evaluate=None):
+    return math.fsum(factor_error(arr, values, f, evaluate) for f in range(arr.n_factors))
 
 
-def dense_system(arr, values):
-    """(J, b) of the whole linearized graph: rows = factor rows in graph order, columns = the packed tangent vector."""
+def dense_system(arr, values, evaluate=None, blocks=None):
+    """(J, b) of the whole linearized graph: rows = factor rows in graph order, columns = the packed tangent vector;
+    `blocks`: the factors' [A b] where the caller holds them already."""
     to = arr.tangent_offsets()
     rows = int(arr.f_rows.sum())
     J, b, r0 = np.zeros((rows, int(to[-1]))), np.zeros(rows), 0
     for f in range(arr.n_factors):
-        Ab, _ = linearized(arr, values, f)
+        Ab = blocks[f] if blocks is not None else linearized(arr, values, f, evaluate)[0]
         m, c0 = Ab.shape[0], 0
         for v in factor_parts(arr, f)[1]:
             d = int(arr.var_dims[v])
