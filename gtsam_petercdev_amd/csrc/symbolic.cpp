@@ -650,6 +650,10 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
     if (lean) S.cls[f] = 0;
     else if ((S.N[f] > kSmallMaxN && !S.med[f]) || cap[f] || S.con[f]) S.cls[f] = 2;
     else if (childless && S.F[f] <= kLeafMaxF) S.cls[f] = 0;
+    if (S.cls[f] == 0 && S.med[f]) {  // a leaf-kernel front after all (lean, or childless with few frontal scalars): not medium
+      S.med[f] = 0;
+      S.n_medium--;
+    }
     if (S.cls[f] == 2) S.n_big++; else S.n_small++;
     int64_t sz = lean ? (int64_t)S.N[f] * S.F[f] : (int64_t)S.N[f] * S.N[f];
     if (S.cls[f] == 2) sz = ((sz + 1) & ~int64_t(1)) + (int64_t)S.N[f] * S.F[f];  // + L-panel area (kernels.h)
