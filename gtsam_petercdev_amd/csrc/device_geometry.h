@@ -383,4 +383,67 @@ __device__ inline bool stereo_project(const double* pose, const double* pt, cons
   return true;
 }
 
+// ---- body_P_sensor (GenericProjectionFactor / GenericStereoFactor: the if(body_P_sensor_) branch of
+// gtsam/slam/ProjectionFactor.h:138-166, StereoFactor.h:126-154; RangeFactorWithTransform, gtsam/sam/RangeFactor.h:131-138):
+// the measurement is taken from pose.compose(sensor), and its pose Jacobian is multiplied from the right by
+// D compose / D pose = AdjointMap(sensor^-1) (Pose3.cpp:61-75, Pose2.cpp:127-135).
+// pose (R9 t3) <- pose * sensor
+__device__ __forceinline__ void pose3_compose_sensor(double* pose, const double* sensor) {
+  store_pose3(compose(load_pose3(pose), load_pose3(sensor)), pose);
+}
+// h (one row of a pose Jacobian: omega 3, v 3) <- h AdjointMap(S^-1), S = (R, t) the sensor pose.  AdjointMap(S^-1) =
+// [R' 0; -R' [t]x, R'], so the row becomes (R h_w + t x (R h_v), R h_v): two rotations and a cross product, no 6 x 6 matrix
+__device__ __forceinline__ void row_times_sensor_adjoint(double* h, const double* sensor) {
+  const P3 S = load_pose3(sensor);
+  const V3 rv = mulv(S.R, V3{h[3], h[4], h[5]});
+  const V3 rw = mulv(S.R, V3{h[0], h[1], h[2]}) + cross(S.t, rv);
+  h[0] = rw.x; h[1] = rw.y; h[2] = rw.z;
+  h[3] = rv.x; h[4] = rv.y; h[5] = rv.z;
+}
+// Pose2: the composed pose as (x, y, c, s) (Rot2 operator* normalizes, Rot2.cpp:27-30,56-64); sensor = (x, y, theta)
+__device__ __forceinline__ P2 pose2_compose_sensor(const double* pose, const double* sensor) {
+  return compose(load_pose2(pose), load_pose2(sensor));
+}
+// h (1 x 3 row of a Pose2 Jacobian) <- h AdjointMap(S^-1); AdjointMap of (x, y, c, s) = [c -s y; s c -x; 0 0 1]
+__device__ __forceinline__ void row_times_sensor_adjoint2(double* h, const double* sensor) {
+  const P2 Si = inverse(load_pose2(sensor));
+  const double h0 = h[0], h1 = h[1], h2 = h[2];
+  h[0] = h0 * Si.c + h1 * Si.s;
+  h[1] = -h0 * Si.s + h1 * Si.c;
+  h[2] = h0 * Si.y - h1 * Si.x + h2;
+}
+// Pose2::range at a pose given as (x, y, c, s): range_2d with the rotation handed in
+__device__ inline double range_2d_cs(const P2& pose, const double* pt, double* H1, double* Dd) {
+  const double dx = pt[0] - pose.x, dy = pt[1] - pose.y;
+  const double r = sqrt(dx * dx + dy * dy);
+  if (H1) {
+    const bool far = fabs(r) > 1e-10;
+    const double rx = far ? dx / r : 1.0, ry = far ? dy / r : 1.0;
+    H1[0] = -rx * pose.c - ry * pose.s; H1[1] = rx * pose.s - ry * pose.c; H1[2] = 0.0;
+    Dd[0] = rx; Dd[1] = ry;
+  }
+  return r;
+}
+
+// ---- PinholeCamera<Cal3_S2>::project with the calibration a variable (GeneralSFMFactor2, gtsam/slam/
+// GeneralSFMFactor.h:264-278; PinholeCamera.h _project: pn = PinholeBase::project2, pi = Cal3_S2::uncalibrate(pn, Dcal,
+// Dpi_pn), gtsam/geometry/Cal3_S2.cpp:54-62).  pose: R9 t3; K = (fx, fy, s, u0, v0).  H1 2x6 / H2 2x3 / H3 2x5 row-major when
+// H1 is non-null; Dcal = [x 0 y 1 0; 0 y 0 0 1].  Returns false on cheirality.
+__device__ inline bool pinhole_project_s2_cal(const double* pose, const double* pt, const double* K, double* pi, double* H1,
+                                              double* H2, double* H3) {
+  if (!pinhole_project_s2(pose, pt, K, pi, H1, H2)) return false;
+  if (H1) {
+    // the intrinsic coordinates again (the same operations as in pinhole_project_s2: the compiler merges them)
+    const double dx = pt[0] - pose[9], dy = pt[1] - pose[10], dz = pt[2] - pose[11];
+    const double qx = pose[0] * dx + pose[3] * dy + pose[6] * dz;
+    const double qy = pose[1] * dx + pose[4] * dy + pose[7] * dz;
+    const double qz = pose[2] * dx + pose[5] * dy + pose[8] * dz;
+    const double d = 1.0 / qz;
+    const double u = qx * d, v = qy * d;
+    H3[0] = u; H3[1] = 0.0; H3[2] = v; H3[3] = 1.0; H3[4] = 0.0;
+    H3[5] = 0.0; H3[6] = v; H3[7] = 0.0; H3[8] = 0.0; H3[9] = 1.0;
+  }
+  return true;
+}
+
 }  // namespace gsxd

@@ -164,20 +164,28 @@ __host__ __device__ inline i64 big_panel_offset(int n) { return ((i64)n * n + 1)
 // (a RangeFactor variant is a family), TL_GENERIC for the rare runtime-dimension ones.  GSX_F_LINEAR is in none.
 enum { TL_SFM = 0, TL_BETWEEN_POSE2 = 1, TL_BETWEEN_POSE3 = 2, TL_GENERIC = 3, TL_PROJECTION = 4, TL_BEARINGRANGE = 5,
        TL_RANGE_POSE2_POINT = 6, TL_RANGE_POSE2_POSE = 7, TL_RANGE_POSE3_POINT = 8, TL_RANGE_POSE3_POSE = 9,
-       TL_BEARING = 10, TL_STEREO = 11, kNumTypeLists = 12 };
-// list of a factor of type `t` whose first two variables have types vt0, vt1 (-1: GSX_F_LINEAR, no list)
-inline int type_list_of(int t, int vt0, int vt1) {
+       TL_BEARING = 10, TL_STEREO = 11,
+       // the forms that carry body_P_sensor behind their measurement (the same kernels with a compile-time switch), and
+       // GeneralSFMFactor2
+       TL_PROJECTION_SENSOR = 12, TL_STEREO_SENSOR = 13, TL_RANGE_POSE2_POINT_SENSOR = 14, TL_RANGE_POSE2_POSE_SENSOR = 15,
+       TL_RANGE_POSE3_POINT_SENSOR = 16, TL_RANGE_POSE3_POSE_SENSOR = 17, TL_SFM2 = 18, kNumTypeLists = 19 };
+constexpr int kSensorListShift = TL_RANGE_POSE2_POINT_SENSOR - TL_RANGE_POSE2_POINT;  // range list -> its sensor form
+// list of a factor of type `t` whose first two variables have types vt0, vt1 and whose measurement has nmeas doubles
+// (the sensor forms are told by their length); -1: GSX_F_LINEAR, no list
+inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
   switch (t) {
     case GSX_F_LINEAR: return -1;
     case GSX_F_SFM: return TL_SFM;
-    case GSX_F_PROJECTION: return TL_PROJECTION;
+    case GSX_F_SFM2: return TL_SFM2;
+    case GSX_F_PROJECTION: return nmeas > 7 ? TL_PROJECTION_SENSOR : TL_PROJECTION;
     case GSX_F_BEARINGRANGE: return TL_BEARINGRANGE;
     case GSX_F_BETWEEN: return vt0 == GSX_VAR_POSE2 ? TL_BETWEEN_POSE2 : (vt0 == GSX_VAR_POSE3 ? TL_BETWEEN_POSE3 : TL_GENERIC);
     case GSX_F_RANGE:
-      return vt0 == GSX_VAR_POSE2 ? (vt1 == GSX_VAR_POSE2 ? TL_RANGE_POSE2_POSE : TL_RANGE_POSE2_POINT)
-                                  : (vt1 == GSX_VAR_POSE3 ? TL_RANGE_POSE3_POSE : TL_RANGE_POSE3_POINT);
+      return (vt0 == GSX_VAR_POSE2 ? (vt1 == GSX_VAR_POSE2 ? TL_RANGE_POSE2_POSE : TL_RANGE_POSE2_POINT)
+                                   : (vt1 == GSX_VAR_POSE3 ? TL_RANGE_POSE3_POSE : TL_RANGE_POSE3_POINT)) +
+             (nmeas > 1 ? kSensorListShift : 0);
     case GSX_F_BEARING: return TL_BEARING;
-    case GSX_F_STEREO: return TL_STEREO;
+    case GSX_F_STEREO: return nmeas > 9 ? TL_STEREO_SENSOR : TL_STEREO;
   }
   return TL_GENERIC;
 }

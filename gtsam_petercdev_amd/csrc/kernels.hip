@@ -293,9 +293,11 @@ __global__ void __launch_bounds__(256) linearize_bearingrange_kernel(DevProblem 
   whiten_store<2, 6>(J, P.f_noise_kind[f], P.noise + P.f_noise_off[f], jac + P.f_jac_off[f]);
 }
 
-// GenericProjectionFactor<Pose3,Point3,Cal3_S2>::evaluateError — gtsam/slam/ProjectionFactor.h:138-166
+// GenericProjectionFactor<Pose3,Point3,Cal3_S2>::evaluateError — gtsam/slam/ProjectionFactor.h:138-166; SENSOR: its
+// if(body_P_sensor_) branch (the sensor pose follows the 7 measurement doubles), the camera at pose * body_P_sensor
+template <bool SENSOR>
 __global__ void __launch_bounds__(256) linearize_projection_kernel(DevProblem P, const int* list, int n, const double* values,
-                                                                   double* jac) {
+                                                                   double* jac, DevStatus* status) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int f = list[i];
@@ -309,7 +311,12 @@ __global__ void __launch_bounds__(256) linearize_projection_kernel(DevProblem P,
   p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
 #pragma unroll
   for (int k = 0; k < 5; ++k) K[k] = z[2 + k];
+  if constexpr (SENSOR) pose3_compose_sensor(pr, z + 7);
   if (pinhole_project_s2(pr, p3, K, pi, H1, H2)) {
+    if constexpr (SENSOR) {  // *H1 = *H1 * H0 (:148)
+      row_times_sensor_adjoint(H1, z + 7);
+      row_times_sensor_adjoint(H1 + 6, z + 7);
+    }
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
       J[2 * c] = H1[c];
@@ -326,6 +333,7 @@ __global__ void __launch_bounds__(256) linearize_projection_kernel(DevProblem P,
 #pragma unroll
     for (int k = 0; k < 18; ++k) J[k] = 0;
     J[18] = J[19] = -2.0 * K[0];
+    if constexpr (SENSOR) atomicAdd(&status->n_cheirality, 1);
   }
   whiten_store<2, 10>(J, P.f_noise_kind[f], P.noise + P.f_noise_off[f], jac + P.f_jac_off[f]);
 }
@@ -429,7 +437,9 @@ __global__ void linearize_generic_kernel(DevProblem P, const int* list, int n, c
 // RangeFactor<A1,A2> — gtsam/sam/RangeFactor.h (ExpressionFactor: e = range(a1, a2) - z, b = -e); V1 = POSE2 | POSE3,
 // V2 = VECTOR (a point of the pose's space) or V1 (a second pose: the range to its translation).  One row:
 // [A b] is 1 x (d1 + d2 + 1).
-template <int V1, int V2>
+// SENSOR: RangeFactorWithTransform (RangeFactor.h:104-150) — body_T_sensor follows the range in the measurement, in the
+// state layout of V1; the range is taken from a1 * body_T_sensor.
+template <int V1, int V2, bool SENSOR>
 __global__ void __launch_bounds__(256) linearize_range_kernel(DevProblem P, const int* list, int n, const double* values,
                                                               double* jac) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -441,7 +451,13 @@ __global__ void __launch_bounds__(256) linearize_range_kernel(DevProblem P, cons
   if constexpr (V1 == GSX_VAR_POSE2) {
     constexpr int NC = (V2 == GSX_VAR_POSE2) ? 7 : 6;
     double ps[3] = {a1[0], a1[1], a1[2]}, p2[2] = {a2[0], a2[1]}, H1[3], Dd[2], J[NC];
-    const double r = range_2d(ps, p2, H1, Dd);
+    double r;
+    if constexpr (SENSOR) {
+      r = range_2d_cs(pose2_compose_sensor(ps, P.meas + fr.meas_off + 1), p2, H1, Dd);
+      row_times_sensor_adjoint2(H1, P.meas + fr.meas_off + 1);
+    } else {
+      r = range_2d(ps, p2, H1, Dd);
+    }
     J[0] = H1[0]; J[1] = H1[1]; J[2] = H1[2];
     if constexpr (V2 == GSX_VAR_POSE2) {  // D d / D other = [R_other 0] (Pose2.cpp:302-308)
       const double c2 = cos(a2[2]), s2 = sin(a2[2]);
@@ -457,7 +473,9 @@ __global__ void __launch_bounds__(256) linearize_range_kernel(DevProblem P, cons
     double pr[12], p3[3] = {a2[TO], a2[TO + 1], a2[TO + 2]}, H1[6], H2[3], J[NC];
 #pragma unroll
     for (int k = 0; k < 12; ++k) pr[k] = a1[k];
+    if constexpr (SENSOR) pose3_compose_sensor(pr, P.meas + fr.meas_off + 1);
     const double r = range_3d(pr, p3, H1, H2);
+    if constexpr (SENSOR) row_times_sensor_adjoint(H1, P.meas + fr.meas_off + 1);
 #pragma unroll
     for (int c = 0; c < 6; ++c) J[c] = H1[c];
     if constexpr (V2 == GSX_VAR_POSE3) {  // [0 0 0, D_local_point R_other] (Pose3.cpp:425-431)
@@ -488,9 +506,12 @@ __global__ void __launch_bounds__(256) linearize_bearing_kernel(DevProblem P, co
   whiten_store<1, 6>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
 }
 
-// GenericStereoFactor<Pose3,Point3>::evaluateError — gtsam/slam/StereoFactor.h:126-154
+// GenericStereoFactor<Pose3,Point3>::evaluateError — gtsam/slam/StereoFactor.h:126-154; SENSOR: its if(body_P_sensor_)
+// branch (the sensor pose follows the 9 measurement doubles).  The adjoint is applied a row at a time (two rotations and a
+// cross product on the six doubles of the row), never as a 6 x 6 matrix: no registers beyond the row's own
+template <bool SENSOR>
 __global__ void __launch_bounds__(256) linearize_stereo_kernel(DevProblem P, const int* list, int n, const double* values,
-                                                               double* jac) {
+                                                               double* jac, DevStatus* status) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const FactorRec fr = P.frec[list[i]];
@@ -503,7 +524,12 @@ __global__ void __launch_bounds__(256) linearize_stereo_kernel(DevProblem P, con
   p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
 #pragma unroll
   for (int k = 0; k < 6; ++k) K[k] = z[3 + k];
+  if constexpr (SENSOR) pose3_compose_sensor(pr, z + 9);
   if (stereo_project(pr, p3, K, pi, H1, H2)) {
+    if constexpr (SENSOR) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) row_times_sensor_adjoint(H1 + 6 * r, z + 9);
+    }
 #pragma unroll
     for (int c = 0; c < 6; ++c)
 #pragma unroll
@@ -518,8 +544,53 @@ __global__ void __launch_bounds__(256) linearize_stereo_kernel(DevProblem P, con
 #pragma unroll
     for (int k = 0; k < 27; ++k) J[k] = 0;
     J[27] = J[28] = J[29] = -2.0 * K[0];
+    if constexpr (SENSOR) atomicAdd(&status->n_cheirality, 1);
   }
   whiten_store<3, 10>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+
+// GeneralSFMFactor2<Cal3_S2>::evaluateError — gtsam/slam/GeneralSFMFactor.h:264-278: keys (pose, point, K); [A b] is
+// 2 x (6 + 3 + 5 + 1).  Cheirality: zero Jacobians and a zero error (:270-277)
+__global__ void __launch_bounds__(256) linearize_sfm2_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                             double* jac, DevStatus* status) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int f = list[i];
+  const FactorRec fr = P.frec[f];
+  const double* pose = values + fr.s0;
+  const double* pt = values + fr.s1;
+  const double* cal = values + P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]];  // (the record holds two state offsets)
+  const double* z = P.meas + fr.meas_off;
+  double pr[12], p3[3], K[5], pi[2], H1[12], H2[6], H3[10], J[30];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) pr[k] = pose[k];
+  p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) K[k] = cal[k];
+  if (pinhole_project_s2_cal(pr, p3, K, pi, H1, H2, H3)) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      J[2 * c] = H1[c];
+      J[2 * c + 1] = H1[6 + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      J[12 + 2 * c] = H2[c];
+      J[12 + 2 * c + 1] = H2[3 + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      J[18 + 2 * c] = H3[c];
+      J[18 + 2 * c + 1] = H3[5 + c];
+    }
+    J[28] = z[0] - pi[0];  // b = -(h(x) - z)
+    J[29] = z[1] - pi[1];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 30; ++k) J[k] = 0;
+    atomicAdd(&status->n_cheirality, 1);
+  }
+  whiten_store<2, 15>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
 }
 
 void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
@@ -547,18 +618,31 @@ void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeL
   }
   if (gn) linearize_generic_kernel<<<grid(gn), 256, 0, st>>>(P, glist, gn, values, jac);
   if (type_counts[4])
-    linearize_projection_kernel<<<grid(type_counts[4]), 256, 0, st>>>(P, type_lists[4], type_counts[4], values, jac);
+    linearize_projection_kernel<false><<<grid(type_counts[4]), 256, 0, st>>>(P, type_lists[4], type_counts[4], values, jac,
+                                                                             status);
   if (type_counts[5])
     linearize_bearingrange_kernel<<<grid(type_counts[5]), 256, 0, st>>>(P, type_lists[5], type_counts[5], values, jac);
   auto run = [&](auto kernel, int k) {
     if (type_counts[k]) kernel<<<grid(type_counts[k]), 256, 0, st>>>(P, type_lists[k], type_counts[k], values, jac);
   };
-  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_VECTOR>, TL_RANGE_POSE2_POINT);
-  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_POSE2>, TL_RANGE_POSE2_POSE);
-  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR>, TL_RANGE_POSE3_POINT);
-  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3>, TL_RANGE_POSE3_POSE);
+  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_VECTOR, false>, TL_RANGE_POSE2_POINT);
+  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_POSE2, false>, TL_RANGE_POSE2_POSE);
+  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR, false>, TL_RANGE_POSE3_POINT);
+  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3, false>, TL_RANGE_POSE3_POSE);
   run(linearize_bearing_kernel, TL_BEARING);
-  run(linearize_stereo_kernel, TL_STEREO);
+  // the kernels that count their cheirality factors
+  auto run_s = [&](auto kernel, int k) {
+    if (type_counts[k]) kernel<<<grid(type_counts[k]), 256, 0, st>>>(P, type_lists[k], type_counts[k], values, jac, status);
+  };
+  run_s(linearize_stereo_kernel<false>, TL_STEREO);
+  // the forms with body_P_sensor, and GeneralSFMFactor2
+  run_s(linearize_projection_kernel<true>, TL_PROJECTION_SENSOR);
+  run_s(linearize_stereo_kernel<true>, TL_STEREO_SENSOR);
+  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_VECTOR, true>, TL_RANGE_POSE2_POINT_SENSOR);
+  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_POSE2, true>, TL_RANGE_POSE2_POSE_SENSOR);
+  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR, true>, TL_RANGE_POSE3_POINT_SENSOR);
+  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3, true>, TL_RANGE_POSE3_POSE_SENSOR);
+  run_s(linearize_sfm2_kernel, TL_SFM2);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -566,7 +650,8 @@ void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeL
 // ---------------------------------------------------------------------------------------------
 // FT / FV >= 0: the factor type / the type of its first variable are known at compile time (the per-type kernels below:
 // the one-kernel-for-all form needed 247 registers, two waves a SIMD); -1: read from the record.
-template <int FT = -1, int FV = -1>
+// SENSOR: the form with body_P_sensor behind the measurement (projection, stereo, range: kernels of their own only).
+template <int FT = -1, int FV = -1, bool SENSOR = false>
 __device__ inline double factor_error(const DevProblem& P, int f, const double* values) {
   const FactorRec fr = P.frec[f];
   const int type = FT >= 0 ? FT : (fr.type_kind & 0xff);
@@ -604,6 +689,7 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
     p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
 #pragma unroll
     for (int k = 0; k < 5; ++k) K[k] = z[2 + k];
+    if constexpr (SENSOR) pose3_compose_sensor(pr, z + 7);
     if (pinhole_project_s2(pr, p3, K, pi, nullptr, nullptr)) {
       e[0] = pi[0] - z[0];
       e[1] = pi[1] - z[1];
@@ -617,7 +703,8 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
     const double* a1 = values + fr.s0;
     const double* a2 = values + fr.s1;  // a point, or a pose whose translation comes first
     double ps[3] = {a1[0], a1[1], a1[2]}, p2[2] = {a2[0], a2[1]}, e[1];
-    e[0] = range_2d(ps, p2, nullptr, nullptr) - z[0];
+    if constexpr (SENSOR) e[0] = range_2d_cs(pose2_compose_sensor(ps, z + 1), p2, nullptr, nullptr) - z[0];
+    else e[0] = range_2d(ps, p2, nullptr, nullptr) - z[0];
     return whitened_half_sqnorm<1>(e, kind, np);
   }
   if constexpr (FT == GSX_F_RANGE && FV == GSX_VAR_POSE3) {
@@ -626,6 +713,7 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
     double pr[12], p3[3] = {a2[0], a2[1], a2[2]}, e[1];
 #pragma unroll
     for (int k = 0; k < 12; ++k) pr[k] = a1[k];
+    if constexpr (SENSOR) pose3_compose_sensor(pr, z + 1);
     e[0] = range_3d(pr, p3, nullptr, nullptr) - z[0];
     return whitened_half_sqnorm<1>(e, kind, np);
   }
@@ -646,6 +734,7 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
     p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
 #pragma unroll
     for (int k = 0; k < 6; ++k) K[k] = z[3 + k];
+    if constexpr (SENSOR) pose3_compose_sensor(pr, z + 9);
     if (stereo_project(pr, p3, K, pi, nullptr, nullptr)) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) e[r] = pi[r] - z[r];
@@ -653,6 +742,21 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
       e[0] = e[1] = e[2] = 2.0 * K[0];
     }
     return whitened_half_sqnorm<3>(e, kind, np);
+  }
+  if constexpr (FT == GSX_F_SFM2) {  // GeneralSFMFactor2: zero behind the camera (GeneralSFMFactor.h:270-277)
+    const double* pose = values + fr.s0;
+    const double* pt = values + fr.s1;
+    const double* cal = values + P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]];
+    double pr[12], p3[3], K[5], pi[2], e[2];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pr[k] = pose[k];
+    p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) K[k] = cal[k];
+    if (!pinhole_project_s2(pr, p3, K, pi, nullptr, nullptr)) return 0.0;
+    e[0] = pi[0] - z[0];
+    e[1] = pi[1] - z[1];
+    return whitened_half_sqnorm<2>(e, kind, np);
   }
   const int vt = FV >= 0 ? FV : ((fr.type_kind >> 24) & 0xff);
   if (type == GSX_F_BETWEEN && vt == GSX_VAR_POSE2) {
@@ -712,12 +816,12 @@ __global__ void __launch_bounds__(256) reduce_final_pair_kernel(const double* pa
 }
 
 // the factors of one type list (the lists of launch_linearize), the type a compile-time constant
-template <int FT, int FV>
+template <int FT, int FV, bool SENSOR = false>
 __global__ void __launch_bounds__(256) error_list_kernel(DevProblem P, const int* list, int n, const double* values,
                                                          double* partials) {
   double acc = 0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    acc += factor_error<FT, FV>(P, list[i], values);
+    acc += factor_error<FT, FV, SENSOR>(P, list[i], values);
   const double s = block_sum(acc);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
@@ -729,12 +833,17 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
   // list order, block order: deterministic
   long long total = 0;
   for (int k = 0; k < kNumTypeLists; ++k) total += type_counts[k];
+  // slots held back so that a list of few factors still gets its block: one per list a graph can fill.  A graph without
+  // the sensor forms and GSX_F_SFM2 keeps the shares — hence the summation order, hence the bits — it had before they came
+  bool new_lists = false;
+  for (int k = TL_PROJECTION_SENSOR; k < kNumTypeLists; ++k) new_lists = new_lists || type_counts[k] > 0;
+  const int held = new_lists ? kNumTypeLists : TL_PROJECTION_SENSOR;
   int off = 0;
   for (int k = 0; k < kNumTypeLists; ++k) {
     const int n = type_counts[k];
     if (!n) continue;
     int nb = (n + 255) / 256;
-    const int share = (int)std::max<long long>(1, (long long)(cap - kNumTypeLists) * n / std::max<long long>(total, 1));
+    const int share = (int)std::max<long long>(1, (long long)(cap - held) * n / std::max<long long>(total, 1));
     nb = std::min(nb, share);
     double* out = partials + off;
     switch (k) {
@@ -749,6 +858,13 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
       case TL_RANGE_POSE3_POSE: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_BEARING: error_list_kernel<GSX_F_BEARING, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_STEREO: error_list_kernel<GSX_F_STEREO, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_PROJECTION_SENSOR: error_list_kernel<GSX_F_PROJECTION, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_STEREO_SENSOR: error_list_kernel<GSX_F_STEREO, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_RANGE_POSE2_POINT_SENSOR:
+      case TL_RANGE_POSE2_POSE_SENSOR: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE2, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_RANGE_POSE3_POINT_SENSOR:
+      case TL_RANGE_POSE3_POSE_SENSOR: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_SFM2: error_list_kernel<GSX_F_SFM2, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       default: error_list_kernel<-1, -1><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
     }
     off += nb;

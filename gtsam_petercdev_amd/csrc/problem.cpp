@@ -102,19 +102,26 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
       case GSX_F_BEARINGRANGE:
         ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE2 && tv(1) == GSX_VAR_VECTOR && dv(1) == 2 && m == 2 && nmeas == 2;
         break;
-      case GSX_F_PROJECTION:
-        ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && m == 2 && nmeas == 7;
+      case GSX_F_PROJECTION:  // 7, or 7 + 12 with body_P_sensor
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && m == 2 &&
+             (nmeas == 7 || nmeas == 7 + 12);
         break;
-      case GSX_F_RANGE:  // (POSE2 | POSE3) to a point of its space or to a pose of its kind
+      case GSX_F_RANGE:  // (POSE2 | POSE3) to a point of its space or to a pose of its kind; + the first key's state
+                         // layout with body_T_sensor
         ok = ok && nk == 2 && (tv(0) == GSX_VAR_POSE2 || tv(0) == GSX_VAR_POSE3) &&
              (tv(1) == tv(0) || (tv(1) == GSX_VAR_VECTOR && dv(1) == (tv(0) == GSX_VAR_POSE2 ? 2 : 3))) && m == 1 &&
-             nmeas == 1;
+             (nmeas == 1 || nmeas == 1 + state_dim(tv(0), dv(0)));
         break;
       case GSX_F_BEARING:
         ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE2 && tv(1) == GSX_VAR_VECTOR && dv(1) == 2 && m == 1 && nmeas == 1;
         break;
       case GSX_F_STEREO:
-        ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && m == 3 && nmeas == 9;
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && m == 3 &&
+             (nmeas == 9 || nmeas == 9 + 12);
+        break;
+      case GSX_F_SFM2:
+        ok = ok && nk == 3 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && tv(2) == GSX_VAR_VECTOR &&
+             dv(2) == 5 && m == 2 && nmeas == 2;
         break;
       default:
         ok = false;

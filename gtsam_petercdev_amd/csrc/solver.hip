@@ -355,10 +355,12 @@ void timers_resolve(gsx_context* c) {
   }
 }
 
-// the list of factor f (kernels.h: type_list_of; the types of its first two variables pick the family's variant)
+// the list of factor f (kernels.h: type_list_of; the types of its first two variables pick the family's variant, the
+// length of its measurement the form with body_P_sensor)
 static int factor_type_list(const HostProblem& P, int f) {
   const int kp = P.f_key_ptr[f], nk = P.f_key_ptr[f + 1] - kp;
-  return type_list_of(P.f_type[f], nk > 0 ? P.types[P.f_vars[kp]] : -1, nk > 1 ? P.types[P.f_vars[kp + 1]] : -1);
+  return type_list_of(P.f_type[f], nk > 0 ? P.types[P.f_vars[kp]] : -1, nk > 1 ? P.types[P.f_vars[kp + 1]] : -1,
+                      P.f_meas_ptr[f + 1] - P.f_meas_ptr[f]);
 }
 // factor lists of the linearize kernels (one per factor family) and of the error kernels; `owned` (may be null: all)
 // restricts them to the factors this rank evaluates

@@ -231,6 +231,8 @@ def Point3(x, y, z):
 
 
 def _wrap_value(v):
+    if isinstance(v, Cal3_S2):  # a calibration as a variable: its 5-vector
+        return _Vector(v.vector())
     return v if hasattr(v, "type_code") else _Vector(v)
 
 
@@ -410,7 +412,9 @@ GeneralSFMFactorCal3Bundler = GeneralSFMFactor
 
 
 class Cal3_S2:
-    """gtsam/geometry/Cal3_S2.h: (fx, fy, s, u0, v0), or (fov degrees, w, h) — Cal3_S2.cpp:28-41."""
+    """gtsam/geometry/Cal3_S2.h: (fx, fy, s, u0, v0), or (fov degrees, w, h) — Cal3_S2.cpp:28-41.  As a VALUE (the
+    calibration variable of GeneralSFMFactor2, a PriorFactor<Cal3_S2>) it is the 5-vector: Cal3_S2 retracts by vector
+    addition (Cal3_S2.h: retract / localCoordinates): Values.insert and PriorFactor take it as that vector."""
 
     def __init__(self, *args):
         if len(args) == 3:
@@ -430,11 +434,20 @@ class Cal3_S2:
         return self.v.copy()
 
 
-def GenericProjectionFactor(measured, model, poseKey, pointKey, K: "Cal3_S2"):
-    """GenericProjectionFactor<Pose3, Point3, Cal3_S2>(measured, model, poseKey, pointKey, K) —
-    gtsam/slam/ProjectionFactor.h (no body_P_sensor, default cheirality flags)."""
-    meas = np.concatenate([np.asarray(measured, dtype=float).reshape(2), K.vector()])
-    return _Factor(A.F_PROJECTION, [poseKey, pointKey], 2, meas, model)
+def _sensor_state(body_P_sensor, cls):
+    if not isinstance(body_P_sensor, cls):
+        raise ValueError(f"body_P_sensor must be a {cls.__name__}")
+    return body_P_sensor.state()
+
+
+def GenericProjectionFactor(measured, model, poseKey, pointKey, K: "Cal3_S2", body_P_sensor: Optional["Pose3"] = None):
+    """GenericProjectionFactor<Pose3, Point3, Cal3_S2>(measured, model, poseKey, pointKey, K[, body_P_sensor]) —
+    gtsam/slam/ProjectionFactor.h (default cheirality flags).  With body_P_sensor the camera sits at
+    pose.compose(body_P_sensor) (:138-166)."""
+    meas = [np.asarray(measured, dtype=float).reshape(2), K.vector()]
+    if body_P_sensor is not None:
+        meas.append(_sensor_state(body_P_sensor, Pose3))
+    return _Factor(A.F_PROJECTION, [poseKey, pointKey], 2, np.concatenate(meas), model)
 
 
 GenericProjectionFactorCal3_S2 = GenericProjectionFactor
@@ -466,6 +479,30 @@ def RangeFactor(key1, key2, measured, model):
 
 
 RangeFactor2D = RangeFactorPose2 = RangeFactor3D = RangeFactorPose3 = RangeFactor
+
+
+def RangeFactorWithTransform(key1, key2, measured, model, body_T_sensor):
+    """RangeFactorWithTransform<A1, A2>(key1, key2, measured, model, body_T_sensor) — gtsam/sam/RangeFactor.h:104-150: the
+    range from key1's pose composed with body_T_sensor (a Pose2 or a Pose3: the type of key1's variable, checked when the
+    graph is lowered)."""
+    if not isinstance(body_T_sensor, (Pose2, Pose3)):
+        raise ValueError("body_T_sensor must be a Pose2 or a Pose3")
+    f = _Factor(A.F_RANGE, [key1, key2], 1, np.concatenate([[float(measured)], body_T_sensor.state()]), model)
+    f.sensor_type = body_T_sensor.type_code
+    return f
+
+
+RangeFactorWithTransform2D = RangeFactorWithTransformPose2 = RangeFactorWithTransform
+RangeFactorWithTransform3D = RangeFactorWithTransformPose3 = RangeFactorWithTransform
+
+
+def GeneralSFMFactor2(measured, model, poseKey, landmarkKey, calibKey):
+    """GeneralSFMFactor2<Cal3_S2>(measured, model, poseKey, landmarkKey, calibKey) — gtsam/slam/GeneralSFMFactor.h:208-278:
+    the calibration is the third variable (a Cal3_S2, held as its 5-vector)."""
+    return _Factor(A.F_SFM2, [poseKey, landmarkKey, calibKey], 2, np.asarray(measured, dtype=float).reshape(2), model)
+
+
+GeneralSFMFactor2Cal3_S2 = GeneralSFMFactor2
 
 
 class Cal3_S2Stereo:
@@ -503,11 +540,15 @@ class StereoPoint2:
         return self.v_.copy()
 
 
-def GenericStereoFactor(measured, model, poseKey, landmarkKey, K: "Cal3_S2Stereo"):
-    """GenericStereoFactor<Pose3, Point3>(measured, model, poseKey, landmarkKey, K) — gtsam/slam/StereoFactor.h (no
-    body_P_sensor, default cheirality flags)."""
+def GenericStereoFactor(measured, model, poseKey, landmarkKey, K: "Cal3_S2Stereo", body_P_sensor: Optional["Pose3"] = None):
+    """GenericStereoFactor<Pose3, Point3>(measured, model, poseKey, landmarkKey, K[, body_P_sensor]) —
+    gtsam/slam/StereoFactor.h (default cheirality flags).  With body_P_sensor the stereo camera sits at
+    pose.compose(body_P_sensor) (:126-154)."""
     z = measured.vector() if isinstance(measured, StereoPoint2) else np.asarray(measured, dtype=float).reshape(3)
-    return _Factor(A.F_STEREO, [poseKey, landmarkKey], 3, np.concatenate([z, K.vector()]), model)
+    meas = [z, K.vector()]
+    if body_P_sensor is not None:
+        meas.append(_sensor_state(body_P_sensor, Pose3))
+    return _Factor(A.F_STEREO, [poseKey, landmarkKey], 3, np.concatenate(meas), model)
 
 
 GenericStereoFactor3D = GenericStereoFactor
@@ -632,6 +673,9 @@ class NonlinearFactorGraph:
                         t2 == t1 or (t2 == A.VAR_VECTOR and d2 == (2 if t1 == A.VAR_POSE2 else 3))):
                     raise ValueError(f"RangeFactor between variables {f.keys_}: not (Pose2 | Pose3) to a point of its space "
                                      "or to a pose of its kind")
+                if getattr(f, "sensor_type", t1) != t1:
+                    raise ValueError(f"RangeFactorWithTransform on variables {f.keys_}: body_T_sensor is not of the first "
+                                     "variable's type")
             key_ptr.append(len(fvars))
             meas.append(f.meas)
             meas_ptr.append(meas_ptr[-1] + f.meas.size)

@@ -103,10 +103,17 @@ enum {
                                (camera, point); meas = (u,v)                       */
   GSX_F_PROJECTION = 4,     /* GenericProjectionFactor<Pose3,Point3,Cal3_S2>
                                (gtsam/slam/ProjectionFactor.h:138-166) with a fixed
-                               calibration and no body_P_sensor; keys (POSE3,
-                               VECTOR(3)); meas = (u, v, fx, fy, s, u0, v0).
-                               Cheirality (default flags): zero Jacobians and the
-                               constant error (2 fx, 2 fx)                         */
+                               calibration; keys (POSE3, VECTOR(3)); meas = (u, v,
+                               fx, fy, s, u0, v0), or those 7 followed by
+                               body_P_sensor as a Pose3 state (R row-major 9, t 3):
+                               19 doubles, the if(body_P_sensor_) branch there — the
+                               camera sits at pose.compose(body_P_sensor), the pose
+                               Jacobian is the camera's times D compose / D pose =
+                               AdjointMap(body_P_sensor^-1) (Pose3.cpp:61-75).
+                               Cheirality (default flags; z <= 0 in the SENSOR
+                               frame): zero Jacobians and the constant error
+                               (2 fx, 2 fx); the sensor form counts it in
+                               n_cheirality.  The sensor rotation is taken as given */
   GSX_F_BEARINGRANGE = 5,   /* BearingRangeFactor<Pose2,Point2> (gtsam/sam/
                                BearingRangeFactor.h; Pose2::bearing / range,
                                gtsam/geometry/Pose2.cpp:246-285, Rot2.cpp:119-130);
@@ -116,7 +123,14 @@ enum {
   GSX_F_RANGE = 6,          /* RangeFactor<A1,A2> (gtsam/sam/RangeFactor.h); keys
                                (POSE2, VECTOR(2)), (POSE2, POSE2), (POSE3, VECTOR(3))
                                or (POSE3, POSE3); m = 1; meas = (range); error =
-                               range(a1, a2) - z.  Pose2::range (gtsam/geometry/
+                               range(a1, a2) - z.  RangeFactorWithTransform<A1,A2>
+                               (RangeFactor.h:104-150): meas = (range) followed by
+                               body_T_sensor in the state layout of the first key —
+                               13 doubles for POSE3 (R 9, t 3), 4 for POSE2 (x, y,
+                               theta); the range is taken from a1.compose(
+                               body_T_sensor), the first key's Jacobian is multiplied
+                               by AdjointMap(body_T_sensor^-1), the row of ones
+                               below included.  Pose2::range (gtsam/geometry/
                                Pose2.cpp:271-310), Pose3::range (Pose3.cpp:408-431).
                                At a distance <= 1e-10 the derivative of the norm is
                                the row of ones norm2 / norm3 hand out there
@@ -127,16 +141,29 @@ enum {
                                VECTOR(2)); m = 1; meas = (bearing angle); error = the
                                wrapped bearing difference: the first row of
                                GSX_F_BEARINGRANGE                                  */
-  GSX_F_STEREO = 8          /* GenericStereoFactor<Pose3,Point3> (gtsam/slam/
-                               StereoFactor.h:126-154) with a fixed Cal3_S2Stereo and
-                               no body_P_sensor; keys (POSE3, VECTOR(3)); m = 3; meas =
-                               (uL, uR, v, fx, fy, s, u0, v0, b).  StereoCamera::
+  GSX_F_STEREO = 8,         /* GenericStereoFactor<Pose3,Point3> (gtsam/slam/
+                               StereoFactor.h:126-154) with a fixed Cal3_S2Stereo;
+                               keys (POSE3, VECTOR(3)); m = 3; meas =
+                               (uL, uR, v, fx, fy, s, u0, v0, b), or those 9 followed
+                               by body_P_sensor as a Pose3 state: 21 doubles, the
+                               if(body_P_sensor_) branch there, as GSX_F_PROJECTION.  StereoCamera::
                                project2 (gtsam/geometry/StereoCamera.cpp:37-79): uL =
                                u0 + fx x/z, uR = u0 + fx (x - b)/z, v = v0 + fy y/z —
                                the skew s is carried but, as there, not used.
                                Cheirality (default flags): z <= 0 in the camera frame
                                gives zero Jacobians and the constant error
-                               (2 fx, 2 fx, 2 fx)                                  */
+                               (2 fx, 2 fx, 2 fx); the sensor form counts it in
+                               n_cheirality                                        */
+  GSX_F_SFM2 = 9            /* GeneralSFMFactor2<Cal3_S2> (gtsam/slam/
+                               GeneralSFMFactor.h:208-278): the calibration is a
+                               variable.  Keys (POSE3, VECTOR(3), VECTOR(5)), the
+                               last one Cal3_S2 as (fx, fy, s, u0, v0) — it retracts
+                               by vector addition (Cal3_S2.h); m = 2; meas = (u, v);
+                               error = PinholeCamera<Cal3_S2>(pose, K).project(point)
+                               - z with Dpose, Dpoint and Dcal = [x 0 y 1 0; 0 y 0 0 1]
+                               (Cal3_S2.cpp:54-62).  Cheirality (:270-277): zero
+                               Jacobians and a ZERO error — not the 2 fx of
+                               GSX_F_PROJECTION — counted in n_cheirality          */
 };
 
 /* ---- noise model kinds (gtsam/linear/NoiseModel.cpp) --------------------- */
@@ -271,7 +298,7 @@ typedef struct gsx_stats {
   double ms_linearize, ms_assemble_hessian, ms_factorize, ms_backsolve,
       ms_linear_error, ms_retract, ms_error;
   int64_t n_linearize, n_factorize, n_backsolve, n_error;
-  int64_t n_cheirality;          /* SFM factors zeroed by cheirality in the last linearize */
+  int64_t n_cheirality;          /* SFM / SFM2 / sensor-form factors in their cheirality branch in the last linearize */
   double amalgamation_relax;     /* the amalgamation in effect (the library's choice under GSX_AMALGAMATION_AUTO) */
   int64_t amalgamation_max_frontal_dim;
   int64_t n_medium_fronts;       /* of the LDS fronts: frontal panel in LDS, trailing block in HBM */

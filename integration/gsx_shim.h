@@ -173,10 +173,14 @@ inline bool lower_factor(const gtsam::NonlinearFactor::shared_ptr& f, Lowered& L
   } else if (auto pc = std::dynamic_pointer_cast<PriorFactor<PinholeCamera<Cal3Bundler>>>(f)) {
     pack(pc->prior(), m), L.add_factor(GSX_F_PRIOR, 9, ks, m, kind, np);
   } else if (auto pr = std::dynamic_pointer_cast<GenericProjectionFactor<Pose3, Point3, Cal3_S2>>(f)) {
-    if (pr->body_P_sensor()) return false;
     const Cal3_S2& K = *pr->calibration();
-    L.add_factor(GSX_F_PROJECTION, 2, ks, {pr->measured().x(), pr->measured().y(), K.fx(), K.fy(), K.skew(), K.px(), K.py()},
-                 kind, np);
+    m = {pr->measured().x(), pr->measured().y(), K.fx(), K.fy(), K.skew(), K.px(), K.py()};
+    if (pr->body_P_sensor()) pack(*pr->body_P_sensor(), m);  // the 19-double form: the camera sits at pose * body_P_sensor
+    L.add_factor(GSX_F_PROJECTION, 2, ks, m, kind, np);
+  } else if (auto s2 = std::dynamic_pointer_cast<GeneralSFMFactor2<Cal3_S2>>(f)) {  // keys (pose, landmark, calibration)
+    L.add_factor(GSX_F_SFM2, 2, ks, {s2->measured().x(), s2->measured().y()}, kind, np);
+  } else if (auto pk = std::dynamic_pointer_cast<PriorFactor<Cal3_S2>>(f)) {  // (a calibration variable is its 5-vector)
+    pack(Vector(pk->prior().vector()), m), L.add_factor(GSX_F_PRIOR, 5, ks, m, kind, np);
   } else if (auto br = std::dynamic_pointer_cast<BearingRangeFactor<Pose2, Point2>>(f)) {
     L.add_factor(GSX_F_BEARINGRANGE, 2, ks, {br->measured().bearing().theta(), br->measured().range()}, kind, np);
   } else if (auto r2 = std::dynamic_pointer_cast<RangeFactor<Pose2, Point2>>(f)) {  // (the variant is the variables' types)
@@ -190,14 +194,27 @@ inline bool lower_factor(const gtsam::NonlinearFactor::shared_ptr& f, Lowered& L
   } else if (auto bf = std::dynamic_pointer_cast<BearingFactor<Pose2, Point2>>(f)) {
     L.add_factor(GSX_F_BEARING, 1, ks, {bf->measured().theta()}, kind, np);
   } else if (auto sf = std::dynamic_pointer_cast<GenericStereoFactor<Pose3, Point3>>(f)) {
-    if (sf->body_P_sensor()) return false;
     const Cal3_S2Stereo& K = *sf->calibration();
     const StereoPoint2& z = sf->measured();
-    L.add_factor(GSX_F_STEREO, 3, ks, {z.uL(), z.uR(), z.v(), K.fx(), K.fy(), K.skew(), K.px(), K.py(), K.baseline()}, kind,
-                 np);
+    m = {z.uL(), z.uR(), z.v(), K.fx(), K.fy(), K.skew(), K.px(), K.py(), K.baseline()};
+    if (sf->body_P_sensor()) pack(*sf->body_P_sensor(), m);  // the 21-double form
+    L.add_factor(GSX_F_STEREO, 3, ks, m, kind, np);
   } else {
+    // RangeFactorWithTransform<A1, A2> has device kernels too (GSX_F_RANGE with 1 + 12 / 1 + 3 measurement doubles) but keeps
+    // body_T_sensor_ private with no accessor (gtsam/sam/RangeFactor.h:109): a caller that knows the sensor pose lowers it
+    // by hand with lower_range_with_transform below; found in a graph, it stays a GSX_F_LINEAR slot.
     return false;
   }
+  return true;
+}
+// RangeFactorWithTransform (gtsam/sam/RangeFactor.h:104-150) given its sensor pose (Pose2 or Pose3: the type of key1's value)
+template <class POSE>
+inline bool lower_range_with_transform(const gtsam::NoiseModelFactor& f, double measured, const POSE& body_T_sensor, Lowered& L) {
+  int kind;
+  std::vector<double> np, m{measured};
+  if (!lower_noise(f.noiseModel(), 1, kind, np)) return false;
+  pack(body_T_sensor, m);
+  L.add_factor(GSX_F_RANGE, 1, std::vector<Key>(f.keys().begin(), f.keys().end()), m, kind, np);
   return true;
 }
 
@@ -213,6 +230,7 @@ inline void lower_values(const gtsam::Values& values, Lowered& L, std::vector<do
     else if (auto c = dynamic_cast<const GenericValue<PinholeCamera<Cal3Bundler>>*>(&kv.value)) L.types.push_back(GSX_VAR_CAMERA), L.dims.push_back(9), pack(c->value(), packed);
     else if (auto x = dynamic_cast<const GenericValue<Point3>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(3), pack(Vector(x->value()), packed);
     else if (auto y = dynamic_cast<const GenericValue<Point2>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(2), pack(Vector(y->value()), packed);
+    else if (auto k2 = dynamic_cast<const GenericValue<Cal3_S2>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(5), pack(Vector(k2->value().vector()), packed);  // retracts by addition (Cal3_S2.h)
     else if (auto v = dynamic_cast<const GenericValue<Vector>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back((int)v->value().size()), pack(v->value(), packed);
     else throw std::runtime_error("gsx shim: a value type libgsx has no state layout for");
   }
@@ -241,6 +259,7 @@ inline gtsam::Values unpack_values(const gtsam::Values& like, const std::vector<
       o += 17;
     } else if (dynamic_cast<const GenericValue<Point3>*>(&kv.value)) out.insert(kv.key, Point3(packed[o], packed[o + 1], packed[o + 2])), o += 3;
     else if (dynamic_cast<const GenericValue<Point2>*>(&kv.value)) out.insert(kv.key, Point2(packed[o], packed[o + 1])), o += 2;
+    else if (dynamic_cast<const GenericValue<Cal3_S2>*>(&kv.value)) out.insert(kv.key, Cal3_S2(packed[o], packed[o + 1], packed[o + 2], packed[o + 3], packed[o + 4])), o += 5;
     else {
       const size_t d = kv.value.dim();
       out.insert(kv.key, Vector(Eigen::Map<const Vector>(&packed[o], d)));

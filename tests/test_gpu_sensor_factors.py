@@ -1,0 +1,499 @@
+"""body_P_sensor on GSX_F_PROJECTION / _STEREO / _RANGE and GeneralSFMFactor2 (GSX_F_SFM2) on the device, through the C ABI,
+against the restatements of tests/_sensor_restatement.py (float64) and tests/_mp_sensor_restatement.py (50 digits), which
+tests/test_host_sensor_factors.py pins with the reference's known answers and true derivatives.
+
+Bounds (the project's, tests/test_gpu_factor_types.py and tests/test_gpu_kernel_edges.py): every [A b] block within
+1e-13 max(1, max |block|) of the 50-digit value; the graph error within error_bound; steps within 1e-6 relative of a dense
+solve of the restated normal equations; marginal blocks within 1e-7.  The composed pose adds rounding steps to every entry:
+where a block exceeds the [A b] bound the device is held to the larger of that bound and twice the distance of the float64
+numpy restatement from the 50-digit value on the same block — never to anything taken from the device's own result; the
+worst ratio to the project bound is printed per test."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from gtsam_petercdev_amd import _abi as A
+from gtsam_petercdev_amd import graph as G
+from tests import _factor_restatement as R
+from tests import _mp_sensor_restatement as MS
+from tests import _sensor_restatement as S
+from tests.test_gpu_factor_types import backend, error_bound, run_example
+
+pytestmark = pytest.mark.gpu
+P2, P3, V, CAM = A.VAR_POSE2, A.VAR_POSE3, A.VAR_VECTOR, A.VAR_CAMERA
+_cache = {}
+
+
+def blocks_of(arr, flat):
+    off = arr.jacobian_offsets()
+    return [flat[off[f]:off[f + 1]] for f in range(arr.n_factors)]
+
+
+def check_blocks(arr, got, what, factors=None):
+    """Every [A b] block of `got` (device, flat) against the 50-digit restatement: the pattern of check_linearization of
+    tests/test_gpu_factor_types.py, block by block.  Returns (worst ratio to the project bound, restated cheirality count)."""
+    gb = blocks_of(arr, got)
+    worst, n_cheir, n_wide = 0.0, 0, 0
+    for f in (range(arr.n_factors) if factors is None else factors):
+        want, cheir = MS.linearized(arr, arr.values, f)
+        want = want.reshape(-1, order="F")
+        n_cheir += int(cheir)
+        project = 1e-13 * max(1.0, float(np.max(np.abs(want))))
+        dev = float(np.max(np.abs(gb[f] - want)))
+        bound = project
+        if dev > project:   # how far float64 numpy itself lies from the 50-digit value on this block
+            np_dist = float(np.max(np.abs(S.linearized(arr, arr.values, f)[0].reshape(-1, order="F") - want)))
+            bound, n_wide = max(project, 2.0 * np_dist), n_wide + 1
+        worst = max(worst, dev / project)
+        assert dev <= bound, (what, f, int(arr.f_type[f]), dev, project, bound)
+    print(f"{what}: worst |[A b] - 50-digit| = {worst:.2f} of the per-block bound 1e-13 max(1, max |block|); "
+          f"{n_wide} blocks judged by twice numpy's own distance")
+    return worst, n_cheir
+
+
+def check_linearization(arr, what):
+    be = backend(arr)
+    be.linearize()
+    got = be.jacobians()
+    worst, n_cheir = check_blocks(arr, got, what)
+    scale = max(1.0, float(np.max(np.abs(got))))
+    eg, ew = be.error(), MS.graph_error(arr, arr.values)
+    print(f"{what}: {arr.n_factors} factors, error {eg:.12g} vs {ew:.12g} (diff {abs(eg - ew):.3e}, bound "
+          f"{error_bound(arr, scale, ew):.3e})")
+    assert abs(eg - ew) <= error_bound(arr, scale, ew), (eg, ew)
+    assert be.stats()["n_cheirality"] == n_cheir
+    be.close()
+    return n_cheir
+
+
+# ---- 1. Jacobians and error per variant and noise ----------------------------------------------------------------------
+@pytest.mark.parametrize("noise", ["unit", "isotropic", "diagonal", "gaussian", "huber"])
+@pytest.mark.parametrize("variant", S.VARIANTS)
+def test_jacobians_and_error_match_the_50_digit_restatement(variant, noise):
+    """301 factors of one variant (two blocks of 256 threads, the second partly filled), a different sensor pose per
+    factor with a rotation of 1 to 2.5 rad."""
+    arr = S.random_graph(variant, 301, noise, seed=60 + S.VARIANTS.index(variant))
+    assert arr.n_factors >= 200 and arr.n_factors % 256 != 0
+    assert check_linearization(arr, f"{variant}/{noise}") == 0
+
+
+# ---- 2. mixed lists ----------------------------------------------------------------------------------------------------
+def mixed_graph(with_new=True):
+    """Plain and sensor forms of every type side by side, SFM2, GSX_F_SFM, priors and betweens.  with_new = False: the same
+    graph without the sensor factors and SFM2 (same variables, same order of the remaining factors)."""
+    rng = np.random.default_rng(17)
+    n3, n2, nl, nc = 12, 10, 20, 4
+    var_list, values = [], []
+    cams3 = []
+    for i in range(n3):
+        Rc = R.random_rot3(rng, 0.2)
+        cams3.append(R.pose3_state(Rc, np.array([2.0 * i, rng.uniform(-1, 1), rng.uniform(-1, 1)])))
+        var_list.append((i, P3, 6))
+        values.append(cams3[-1])
+    pts3 = [np.array([rng.uniform(0, 2.0 * n3), rng.uniform(-3, 3), rng.uniform(12, 20)]) for _ in range(nl)]
+    for j in range(nl):
+        var_list.append((1000 + j, V, 3))
+        values.append(pts3[j])
+    for i in range(n2):
+        var_list.append((2000 + i, P2, 3))
+        values.append(np.array([1.5 * i, math.sin(0.4 * i), 0.3 * i]))
+    pts2 = [rng.uniform(-3, 15, 2) for _ in range(8)]
+    for j in range(8):
+        var_list.append((3000 + j, V, 2))
+        values.append(pts2[j])
+    for i in range(nc):      # BAL cameras (GSX_F_SFM)
+        var_list.append((4000 + i, CAM, 9))
+        values.append(np.concatenate([cams3[i], [500.0, -1e-3, 1e-5, 0.0, 0.0]]))
+    var_list.append((5000, V, 5))
+    values.append(np.array(S.K_S2) + np.array([3.0, -2.0, 0.2, 1.0, -1.0]))
+    o3, ol, o2, op2, oc, ok = 0, n3, n3 + nl, n3 + nl + n2, n3 + nl + n2 + 8, n3 + nl + n2 + 8 + nc
+    vals = lambda v: values[v]
+    factors = []
+
+    def add(is_new, *fac):
+        if with_new or not is_new:
+            factors.append(fac)
+    add(False, A.F_PRIOR, [o3], 6, cams3[0], A.NOISE_ISOTROPIC, [0.1])
+    add(False, A.F_PRIOR, [o2], 3, vals(o2), A.NOISE_DIAGONAL, [0.1, 0.1, 0.05])
+    add(False, A.F_PRIOR, [ok], 5, S.K_S2, A.NOISE_DIAGONAL, [50.0, 50.0, 0.1, 10.0, 10.0])
+    for i in range(n3 - 1):
+        Ra, ta = R.pose3_of(cams3[i])
+        Rb, tb = R.pose3_of(cams3[i + 1])
+        add(False, A.F_BETWEEN, [i, i + 1], 6, R.pose3_state(Ra.T @ Rb, Ra.T @ (tb - ta) + 0.01), A.NOISE_ISOTROPIC, [0.1])
+    for i in range(n2 - 1):
+        add(False, A.F_BETWEEN, [o2 + i, o2 + i + 1], 3, R.pose2_between(vals(o2 + i), vals(o2 + i + 1)) + 0.01, A.NOISE_ISOTROPIC, [0.1])
+    for j in range(nl):
+        near = [i for i in range(n3) if abs(2.0 * i - pts3[j][0]) <= 6.0]      # cameras that have the point well in front
+        for i in rng.choice(near, min(4, len(near)), replace=False):
+            i = int(i)
+            sensor = S.random_sensor3(rng)
+            # the camera of a sensor form sits at body * sensor: a mild sensor (up to 0.35 rad) keeps the landmark in front
+            # of it; the range factors, which have no front, get a sensor rotated by 1 to 2.5 rad
+            mild = R.pose3_state(R.so3_expmap(rng.uniform(-0.2, 0.2, 3)), rng.uniform(-0.3, 0.3, 3))
+            cam = S.pose3_compose(cams3[i], mild)[0]
+            z2 = S.s2_project(cams3[i], pts3[j], S.K_S2)[0] + rng.normal(0, 20.0, 2)
+            z2s = S.s2_project(cam, pts3[j], S.K_S2)[0] + rng.normal(0, 20.0, 2)
+            z3 = R.stereo_project(cams3[i], pts3[j], R.STEREO_K)[0] + rng.normal(0, 20.0, 3)
+            z3s = R.stereo_project(cam, pts3[j], R.STEREO_K)[0] + rng.normal(0, 20.0, 3)
+            add(False, A.F_PROJECTION, [i, ol + j], 2, np.concatenate([z2, S.K_S2]), A.NOISE_ISOTROPIC, [2.0])
+            add(True, A.F_PROJECTION, [i, ol + j], 2, np.concatenate([z2s, S.K_S2, mild]), A.NOISE_DIAGONAL, [2.0, 3.0])
+            add(False, A.F_STEREO, [i, ol + j], 3, np.concatenate([z3, R.STEREO_K]), A.NOISE_UNIT, ())
+            add(True, A.F_STEREO, [i, ol + j], 3, np.concatenate([z3s, R.STEREO_K, mild]),
+                A.NOISE_DIAGONAL | A.NOISE_ROBUST_HUBER, [1.0, 2.0, 1.5, 30.0])
+            add(True, S.F_SFM2, [i, ol + j, ok], 2, z2 + 1.0, A.NOISE_ISOTROPIC, [1.5])
+            add(False, A.F_RANGE, [i, ol + j], 1, [R.range_pose3(cams3[i], pts3[j], False)[0] + 0.1], A.NOISE_ISOTROPIC, [0.3])
+            add(True, A.F_RANGE, [i, ol + j], 1, np.concatenate([[R.range_pose3(cams3[i], pts3[j], False)[0] + 0.1], sensor]), A.NOISE_UNIT, ())
+            if i < nc:
+                zs = S.bundler_project(vals(oc + i), pts3[j])[0] + rng.normal(0, 2.0, 2)
+                add(False, A.F_SFM, [oc + i, ol + j], 2, zs, A.NOISE_ISOTROPIC, [1.0])
+    for i in range(n3 - 2):
+        add(False, A.F_RANGE, [i, i + 2], 1, [R.range_pose3(cams3[i], cams3[i + 2], True)[0] - 0.05], A.NOISE_ISOTROPIC, [0.2])
+    # the list with a single factor: one pose-to-pose range with a sensor
+    add(True, A.F_RANGE, [0, 5], 1, np.concatenate([[9.0], S.random_sensor3(rng)]), A.NOISE_ISOTROPIC, [0.2])
+    for i in range(n2):
+        for j in rng.choice(8, 3, replace=False):
+            j = int(j)
+            r = R.range_pose2(vals(o2 + i), pts2[j], False)[0]
+            th = R.bearing_pose2(vals(o2 + i), pts2[j])[0]
+            add(False, A.F_BEARING, [o2 + i, op2 + j], 1, [th - 0.02], A.NOISE_ISOTROPIC, [0.1])
+            add(False, A.F_BEARINGRANGE, [o2 + i, op2 + j], 2, [th + 0.01, r - 0.1], A.NOISE_DIAGONAL, [0.1, 0.3])
+            add(False, A.F_RANGE, [o2 + i, op2 + j], 1, [r + 0.1], A.NOISE_UNIT, ())
+            add(True, A.F_RANGE, [o2 + i, op2 + j], 1, np.concatenate([[r + 0.2], S.random_sensor2(rng)]), A.NOISE_ISOTROPIC, [0.3])
+        if i + 2 < n2:
+            r = R.range_pose2(vals(o2 + i), vals(o2 + i + 2), True)[0]
+            add(False, A.F_RANGE, [o2 + i, o2 + i + 2], 1, [r - 0.1], A.NOISE_ISOTROPIC, [0.2])
+            add(True, A.F_RANGE, [o2 + i, o2 + i + 2], 1, np.concatenate([[r + 0.1], S.random_sensor2(rng)]), A.NOISE_UNIT, ())
+    arr = R.make_arrays(var_list, factors, np.concatenate(values))
+    return R.add_priors(arr, 1.0)
+
+
+def is_new_form(arr, f):
+    return int(arr.f_type[f]) == S.F_SFM2 or S.has_sensor(arr, f)
+
+
+def test_mixed_lists_and_plain_blocks_bit_identical():
+    """Every factor list non-empty side by side (one of them with a single factor), compared factor by factor; and the
+    plain factors' blocks bit-identical to those of the same graph without the sensor factors and SFM2."""
+    arr, plain = mixed_graph(True), mixed_graph(False)
+    kinds = {}
+    for f in range(arr.n_factors):
+        _, vs, z = R.factor_parts(arr, f)
+        key = (int(arr.f_type[f]), int(arr.var_types[vs[0]]), int(arr.var_types[vs[-1]]) if len(vs) > 1 else -1, len(z))
+        kinds[key] = kinds.get(key, 0) + 1
+    lists = [(A.F_SFM, CAM, V, 2), (A.F_BETWEEN, P2, P2, 3), (A.F_BETWEEN, P3, P3, 12), (A.F_PRIOR, P3, -1, 12),
+             (A.F_PROJECTION, P3, V, 7), (A.F_BEARINGRANGE, P2, V, 2), (A.F_RANGE, P2, V, 1), (A.F_RANGE, P2, P2, 1),
+             (A.F_RANGE, P3, V, 1), (A.F_RANGE, P3, P3, 1), (A.F_BEARING, P2, V, 1), (A.F_STEREO, P3, V, 9),
+             (A.F_PROJECTION, P3, V, 19), (A.F_STEREO, P3, V, 21), (A.F_RANGE, P2, V, 4), (A.F_RANGE, P2, P2, 4),
+             (A.F_RANGE, P3, V, 13), (A.F_RANGE, P3, P3, 13), (S.F_SFM2, P3, V, 2)]     # one family per factor list
+    assert all(kinds.get(k, 0) > 0 for k in lists), kinds
+    assert kinds[(A.F_RANGE, P3, P3, 13)] == 1
+    be = backend(arr)
+    be.linearize()
+    got = be.jacobians()
+    _, n_cheir = check_blocks(arr, got, "mixed graph")
+    assert n_cheir == 0 and be.stats()["n_cheirality"] == 0
+    scale = max(1.0, float(np.max(np.abs(got))))
+    eg, ew = be.error(), MS.graph_error(arr, arr.values)
+    assert abs(eg - ew) <= error_bound(arr, scale, ew), (eg, ew)
+    bp = backend(plain)
+    bp.linearize()
+    got_p = blocks_of(plain, bp.jacobians())
+    old = [f for f in range(arr.n_factors) if not is_new_form(arr, f)]
+    assert len(old) == plain.n_factors and 0 < len(old) < arr.n_factors
+    gb = blocks_of(arr, got)
+    for k, f in enumerate(old):
+        assert arr.f_type[f] == plain.f_type[k] and np.array_equal(gb[f], got_p[k]), (f, k)
+    r = be.lm_optimize(A.lm_params_legacy())
+    assert r["final_error"] < r["initial_error"]
+    be.close()
+    bp.close()
+
+
+# ---- 3. known answers through the device -------------------------------------------------------------------------------
+def test_known_answers_through_the_device():
+    """The reference values of tests/test_host_sensor_factors.py through gsx_error / gsx_get_jacobians."""
+    from tests.test_host_factor_types import K9, two_var_graph
+    from tests.test_host_sensor_factors import K_TEST, SENSOR3, pose_at, range_with_transform_graphs
+    be = backend(two_var_graph(P3, 6, pose_at([-6.25, 0.10, -1.0]), V, 3, [0.0, 0.0, 0.0], A.F_PROJECTION, 2,
+                               [323.0, 240.0] + K_TEST + SENSOR3))
+    assert abs(be.error() - 4.5) < 1e-8                               # (9 + 0) / 2
+    be.linearize()
+    Ab = be.jacobians().reshape(2, 10, order="F")
+    H1 = [[-92.376, 0.0, 577.350, 0.0, 92.376, 0.0], [-9.2376, -577.350, 0.0, 0.0, 0.0, 92.376]]
+    H2 = [[0.0, -92.376, 0.0], [0.0, 0.0, -92.376]]
+    assert np.allclose(Ab[:, :6], H1, atol=1e-3) and np.allclose(Ab[:, 6:9], H2, atol=1e-3)
+    assert np.allclose(Ab[:, 9], [3.0, 0.0], atol=1e-9)
+    be.close()
+    be = backend(two_var_graph(P3, 6, pose_at([-6.50, 0.10, -1.0]), V, 3, [0.0, 0.0, 0.0], A.F_STEREO, 3, K9 + SENSOR3))
+    assert abs(be.error() - 7.0) < 1e-8
+    be.linearize()
+    Ab = be.jacobians().reshape(3, 10, order="F")
+    H1 = [[-100.0, 0.0, 650.0, 0.0, 100.0, 0.0], [-100.0, -8.0, 649.2, -8.0, 100.0, 0.0], [-10.0, -650.0, 0.0, 0.0, 0.0, 100.0]]
+    H2 = [[0.0, -100.0, 0.0], [8.0, -100.0, 0.0], [0.0, 0.0, -100.0]]
+    assert np.allclose(Ab[:, :6], H1, atol=1e-3) and np.allclose(Ab[:, 6:9], H2, atol=1e-3)
+    assert np.allclose(Ab[:, 9], [3.0, -2.0, 1.0], atol=1e-9)
+    be.close()
+    for variant, arr in range_with_transform_graphs().items():
+        be = backend(arr)
+        assert abs(be.error() - 0.5 * 0.295630141 ** 2) < 1e-9, variant
+        be.linearize()
+        assert abs(be.jacobians()[-1] + 0.295630141) < 1e-9
+        be.close()
+
+
+# ---- 4. cheirality and zero distance -----------------------------------------------------------------------------------
+def test_cheirality_is_judged_in_the_sensor_frame_and_zero_distance_keeps_the_row_of_ones():
+    from tests.test_host_factor_types import two_var_graph
+    rng = np.random.default_rng(5)
+    # a sensor that looks backwards: a half turn about the body's y axis, 0.2 m behind the body origin
+    back = R.pose3_state(R.so3_expmap(np.array([0.0, math.pi, 0.0])), np.array([0.0, 0.0, -0.2]))
+    body = R.pose3_state(R.random_rot3(rng, 1.0), rng.uniform(-2, 2, 3))
+    Rb, tb = R.pose3_of(body)
+    ahead, astern = tb + Rb @ np.array([0.3, -0.2, 5.0]), tb + Rb @ np.array([0.3, -0.2, -5.0])
+    z2, z3 = [300.0, 200.0] + list(S.K_S2), [300.0, 280.0, 200.0] + list(R.STEREO_K)
+    fx2, fx3 = S.K_S2[0], R.STEREO_K[0]
+    cases = [  # (graph, expected cheirality, rows, 2 fx or None for SFM2's zero)
+        (two_var_graph(P3, 6, body, V, 3, ahead, A.F_PROJECTION, 2, z2 + list(back)), True, 2, 2 * fx2),    # in front of the body, behind the sensor
+        (two_var_graph(P3, 6, body, V, 3, astern, A.F_PROJECTION, 2, z2 + list(back)), False, 2, None),     # the converse
+        (two_var_graph(P3, 6, body, V, 3, ahead, A.F_STEREO, 3, z3 + list(back)), True, 3, 2 * fx3),
+        (two_var_graph(P3, 6, body, V, 3, astern, A.F_STEREO, 3, z3 + list(back)), False, 3, None),
+    ]
+    cam = S.pose3_compose(body, back)[0]
+    for pt, cheir in ((ahead, True), (astern, False)):
+        cases.append((R.make_arrays([(1, P3, 6), (2, V, 3), (3, V, 5)], [(S.F_SFM2, [0, 1, 2], 2, [300.0, 200.0], A.NOISE_ISOTROPIC, [2.0])],
+                                    np.concatenate([cam, pt, S.K_S2])), cheir, 2, 0.0))
+    for arr, cheir, m, const in cases:
+        assert S.evaluate(arr, arr.values, 0)[2] == cheir
+        be = backend(arr)
+        be.linearize()
+        blk = be.jacobians().reshape(m, -1, order="F")
+        assert be.stats()["n_cheirality"] == int(cheir)
+        if cheir:
+            W = R.whitener(arr, 0)[0]
+            assert not np.any(blk[:, :-1]) and np.allclose(blk[:, -1], W @ np.full(m, -const), rtol=1e-14, atol=0)
+            assert abs(be.error() - 0.5 * float(np.sum((W @ np.full(m, const)) ** 2))) <= 1e-13 * max(1.0, m * const * const)
+        else:
+            assert np.any(blk[:, :-1])
+            check_blocks(arr, blk.reshape(-1, order="F"), "in front of the sensor")
+        be.close()
+    # range + sensor with the sensor origin on the landmark: the row of ones times the adjoint
+    s3, s2 = S.random_sensor3(rng), S.random_sensor2(rng)
+    tc = R.pose3_of(S.pose3_compose(body, s3)[0])[1]
+    b2 = np.array([0.7, -1.1, 0.4])
+    for arr in (two_var_graph(P3, 6, body, V, 3, tc, A.F_RANGE, 1, [0.5] + list(s3)),
+                two_var_graph(P3, 6, body, P3, 6, np.concatenate([body[:9], tc]), A.F_RANGE, 1, [0.5] + list(s3)),
+                two_var_graph(P2, 3, b2, V, 2, S.pose2_compose(b2, s2)[0][:2], A.F_RANGE, 1, [0.5] + list(s2))):
+        be = backend(arr)
+        be.linearize()
+        got, want = be.jacobians(), S.jacobians(arr, arr.values)[0]
+        assert np.all(np.isfinite(got)) and np.max(np.abs(got - want)) <= 1e-13 * max(1.0, np.max(np.abs(want)))
+        if arr.var_types[0] == P2:     # Pose2::range: the point's Jacobian IS norm2's row
+            assert np.array_equal(want[3:5], [1.0, 1.0])
+        assert abs(be.error() - 0.125) < 1e-14
+        be.close()
+
+
+# ---- 5. assembly classes of SFM2 ---------------------------------------------------------------------------------------
+def selfcal(n_poses, n_points):
+    """Self-calibration graph; points 1 and 2 are seen by exactly 3 and exactly 6 poses (four term records a factor — own,
+    pose, K, rhs — so 12 and 24 records, both divisible by 3: the star test must refuse them by shape), the others by all."""
+    key = (n_poses, n_points)
+    if key not in _cache:
+        _cache[key] = S.selfcal_graph(n_poses, n_points, seed=3,
+                                      obs_of_point=lambda j: range(3) if j == 1 else (range(6) if j == 2 else range(n_poses)))
+    return _cache[key]
+
+
+def steps_against_dense(arr, what, ordering):
+    be = backend(arr)
+    if not isinstance(ordering, int):
+        be.set_ordering(ordering)
+    elif ordering != A.ORDER_MINDEGREE:
+        be.set_ordering(be.compute_ordering(ordering))
+    be.linearize()
+    J, b = S.dense_system(arr, arr.values)
+    H, g = J.T @ J, J.T @ b
+    worst = 0.0
+    for lam, diag in ((0.0, False), (1e-3, False), (10.0, False), (1e-3, True), (10.0, True)):
+        D = np.diag(np.clip(np.diag(H), 1e-6, 1e32)) if diag else np.eye(H.shape[0])
+        want = np.linalg.solve(H + lam * D, g)
+        got = be.solve(lam, diag)
+        rel = float(np.linalg.norm(got - want) / np.linalg.norm(want))
+        worst = max(worst, rel)
+        assert rel <= 1e-6, (what, lam, diag, rel)
+    st, cl = be.stats(), be.front_classes()
+    print(f"{what}: dim {H.shape[0]}, worst |step - dense| / |dense| = {worst:.3e}; {st['n_fronts']} fronts, classes "
+          f"{np.bincount(cl & 3, minlength=4).tolist()} (leaf, LDS, blocked, medium), {int(((cl >> 3) & 1).sum())} lean")
+    assert len(cl) == st["n_fronts"] and st["n_cheirality"] == 0
+    be.close()
+
+
+@pytest.mark.parametrize("order", ["schur", "mindegree", "K first"])
+@pytest.mark.parametrize("shape", [(6, 5), (8, 8), (12, 20)])
+def test_sfm2_steps_match_a_dense_solve_in_every_assembly_class(shape, order):
+    """Steps at lambda 0, 1e-3 and 10, with and without diagonal damping, against the dense solve.  K eliminated last has two
+    term records per factor (own block, rhs): 6 x 5 gives it 27 observations + its prior = 56 records (below 64: a tile /
+    light variable), 8 x 8 gives 116 and 12 x 20 gives 452 (above: a diag variable).  With K ordered first every landmark's
+    and pose's term list has the three-per-factor shape of a binary factor (own, partner, rhs, at columns 6 / 0 / 14).
+    gsx_get_front_classes / gsx_get_stats tell the elimination class of the fronts, not the H-assembly group of a variable:
+    what they tell is printed and its consistency asserted."""
+    arr = selfcal(*shape)
+    n_obs = int((arr.f_type == S.F_SFM2).sum())
+    n_p, n_l = shape
+    assert n_obs == (n_l - 2) * n_p + 3 + 6 and n_p >= 6
+    if order == "K first":
+        be = backend(arr)
+        keys = [int(k) for k in be.compute_ordering(A.ORDER_SCHUR)]
+        be.close()
+        kk = int(arr.var_keys[-1])
+        ordering = [kk] + [k for k in keys if k != kk]
+    else:
+        ordering = A.ORDER_SCHUR if order == "schur" else A.ORDER_MINDEGREE
+    steps_against_dense(arr, f"self-calibration {n_p} x {n_l}, {order}", ordering)
+
+
+# ---- 6. rig equivalence ------------------------------------------------------------------------------------------------
+def test_rig_equivalence_on_the_stereo_vo_example():
+    """examples/StereoVOExample.py re-expressed with body poses X S^-1 and body_P_sensor = S."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    import StereoVOExample as ex
+    graph, initial = ex.build()
+    Sp = G.Pose3(G.Rot3.RzRyRx(0.4, -0.7, 1.1), [0.3, -0.2, 0.5])
+    rig, rig_initial = G.NonlinearFactorGraph(), G.Values()
+    for f in graph.factors:
+        if f.ftype == A.F_STEREO:
+            rig.add(G.GenericStereoFactor(f.meas[:3], f.noise, f.keys_[0], f.keys_[1], G.Cal3_S2Stereo(*f.meas[3:9]), Sp))
+        else:   # the constraint on the first pose: on the body pose that puts the camera there
+            rig.add(G.PriorFactor(f.keys_[0], G.Pose3.from_state(f.meas).compose(Sp.inverse()), f.noise))
+    for k in initial.keys():
+        v = initial.at(k)
+        rig_initial.insert(k, v.compose(Sp.inverse()) if isinstance(v, G.Pose3) else v)
+    a0, a1 = graph.to_arrays(initial), rig.to_arrays(rig_initial)
+    b0, b1 = backend(a0), backend(a1)
+    e0, e1 = b0.error(), b1.error()
+    b0.linearize()
+    b1.linearize()
+    j0, j1 = blocks_of(a0, b0.jacobians()), blocks_of(a1, b1.jacobians())
+    scale = max(1.0, float(np.max(np.abs(np.concatenate(j0)))))
+    assert abs(e0 - e1) <= error_bound(a0, scale, e0), (e0, e1)
+    n = 0
+    for f in range(a0.n_factors):
+        if a0.f_type[f] == A.F_STEREO:
+            l0, l1 = j0[f].reshape(3, 10, order="F")[:, 6:], j1[f].reshape(3, 10, order="F")[:, 6:]
+            assert np.max(np.abs(l0 - l1)) <= 1e-13 * max(1.0, float(np.max(np.abs(l0)))), f
+            n += 1
+    assert n == 6
+    b0.close()
+    b1.close()
+    params = G.LevenbergMarquardtParams()
+    o0, o1 = G.LevenbergMarquardtOptimizer(graph, initial, params), G.LevenbergMarquardtOptimizer(rig, rig_initial, params)
+    o0.optimize()
+    r1 = o1.optimize()
+    f0, f1 = o0.result["final_error"], o1.result["final_error"]
+    print(f"rig equivalence: start error {e0:.9g} / {e1:.9g}; LM final error {f0:.3e} (plain) / {f1:.3e} (rig)")
+    # the optimizer's own stopping tolerance: LM stops when the decrease falls below relativeErrorTol x the error (or
+    # absoluteErrorTol); two runs that stopped by it agree to that tolerance of the start error
+    assert abs(f0 - f1) <= params.relativeErrorTol * o0.result["initial_error"]
+    x2 = r1.at(2).compose(Sp)
+    assert np.allclose(x2.translation(), [0, 0, 1], atol=1e-5)
+
+
+# ---- 7. the self-calibration example -----------------------------------------------------------------------------------
+def restated_gauss_newton(arr, max_iterations=100, relative_error_tol=1e-5, absolute_error_tol=1e-5, error_tol=0.0):
+    """Dense Gauss-Newton on the restatement under the stopping rule the optimizers share (checkConvergence,
+    gtsam/nonlinear/NonlinearOptimizer.cpp:182-231) with the NonlinearOptimizerParams defaults DoglegOptimizer runs with.
+    Plain Gauss-Newton has no step control and its fourth step from this start raises the error (6.6e-3 -> 1.0): the rule is
+    consulted only after a step that lowered it, where a trust-region method would have rejected the step instead."""
+    vals = arr.values.copy()
+    so, to = arr.state_offsets(), arr.tangent_offsets()
+    e0 = err = S.graph_error(arr, vals)
+    for _ in range(max_iterations):
+        J, b = S.dense_system(arr, vals)
+        d = np.linalg.solve(J.T @ J, J.T @ b)
+        vals = np.concatenate([R.retract(int(arr.var_types[v]), vals[so[v]:so[v + 1]], d[to[v]:to[v + 1]]) for v in range(arr.n_vars)])
+        new = S.graph_error(arr, vals)
+        done = new <= error_tol or (new < err and ((err - new) / err <= relative_error_tol or err - new <= absolute_error_tol))
+        err = new
+        if done:
+            break
+    return e0, err, vals
+
+
+def test_self_calibration_example():
+    """examples/SelfCalibrationExample.py: the problem has zero residual at the truth.  A dense Gauss-Newton on the
+    restatement from the same start, under the same stopping rule, sets the yardstick: the device's Dogleg run must reach
+    the same error reduction less two decades, and bring K back to (50, 50, 0, 50, 50) as closely as the restated run does,
+    times 100.  Measured on MI355X: restated Gauss-Newton 20139.8 -> 2.5e-27, K off by 1.4e-14; device Dogleg
+    20139.8 -> 2.6e-27 in 10 iterations, K off by 2.1e-14."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    import SelfCalibrationExample as ex
+    graph, initial = ex.build()
+    arr = graph.to_arrays(initial)
+    assert int((arr.f_type == S.F_SFM2).sum()) == 64 and arr.n_factors == 67
+    e0, e_gn, v_gn = restated_gauss_newton(arr)
+    truth_K = np.array([50.0, 50.0, 0.0, 50.0, 50.0])
+    k_gn = float(np.max(np.abs(v_gn[:5] - truth_K)))
+    opt = G.DoglegOptimizer(graph, initial)
+    result = opt.optimize()
+    r = opt.result
+    k_dev = float(np.max(np.abs(result.at(G.symbol("K", 0)) - truth_K)))
+    print(f"self-calibration: restated GN {e0:.6g} -> {e_gn:.3e} (K off by {k_gn:.3e}); device Dogleg {r['initial_error']:.6g} -> "
+          f"{r['final_error']:.3e} in {r['iterations']} iterations (K off by {k_dev:.3e})")
+    assert abs(r["initial_error"] - e0) <= 1e-9 * e0
+    assert r["final_error"] / r["initial_error"] <= 100.0 * e_gn / e0
+    assert k_dev <= 100.0 * k_gn
+    text = run_example("SelfCalibrationExample.py")
+    assert "Final results:" in text and "Values with 17 values:" in text and "Value K0: (gtsam::Cal3_S2)" in text
+    m = re.search(r"Cal3_S2\[\n\t([-+0-9.eE]+), ([-+0-9.eE]+), ([-+0-9.eE]+);\n\t0, ([-+0-9.eE]+), ([-+0-9.eE]+);", text)
+    assert np.allclose([float(x) for x in m.groups()], [50, 0, 50, 50, 50], atol=1e-4)
+
+
+# ---- 8. seams ----------------------------------------------------------------------------------------------------------
+def test_partial_relinearization_is_bit_identical_with_sensor_factors_and_sfm2():
+    arr = mixed_graph(True)
+    so = arr.state_offsets()
+    rng = np.random.default_rng(4)
+    # a landmark (its sensor factors and its SFM2 factors go through the partial lists), a Pose2 and a Point2; not K, whose
+    # factors are most of the graph (the call would take the full path)
+    moved = [12 + 7, 12 + 20 + 1, 12 + 20 + 10 + 2]
+    assert [int(arr.var_types[v]) for v in moved] == [V, P2, V] and arr.var_dims[moved[2]] == 2
+    new_states = [R.retract(int(arr.var_types[v]), arr.values[so[v]:so[v + 1]], rng.normal(0, 0.01, int(arr.var_dims[v])))
+                  for v in moved]
+    be = backend(arr, A.ORDER_SCHUR)
+    be.linearize()
+    be.solve(0.0, False)
+    stats = be.relinearize_partial([int(arr.var_keys[v]) for v in moved], np.concatenate(new_states))
+    d_partial, j_partial = be.solve(0.0, False), be.jacobians()
+    vals = be.get_values()
+    full = backend(arr, A.ORDER_SCHUR)
+    full.set_values(vals)
+    full.linearize()
+    d_full, j_full = full.solve(0.0, False), full.jacobians()
+    print("partial relinearization:", stats)
+    assert stats["n_factors_relinearized"] > 0
+    assert np.array_equal(j_partial, j_full) and np.array_equal(d_partial, d_full)
+    be.close()
+    full.close()
+
+
+def test_marginal_covariances_of_the_self_calibration_graph():
+    arr = selfcal(8, 8)
+    be = backend(arr, A.ORDER_SCHUR)
+    be.linearize()
+    blocks = be.marginal_covariances()
+    J, _ = S.dense_system(arr, arr.values)
+    C = np.linalg.inv(J.T @ J)
+    to = arr.tangent_offsets()
+    worst = 0.0
+    for i, k in enumerate(arr.var_keys):
+        co = C[to[i]:to[i + 1], to[i]:to[i + 1]]
+        err = float(np.max(np.abs(blocks[int(k)] - co)) / np.max(np.abs(co)))
+        worst = max(worst, err)
+        assert err <= 1e-7, (int(k), err)
+    print(f"marginals of the 8 x 8 self-calibration graph: {arr.n_vars} blocks, worst relative error {worst:.3e}")
+    be.close()
