@@ -22,6 +22,8 @@ NOISE_FORMAT_G2O, NOISE_FORMAT_TORO, NOISE_FORMAT_GRAPH, NOISE_FORMAT_COV, NOISE
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_CONSTRAINED = range(5)
 NOISE_ROBUST_HUBER, NOISE_ROBUST_TUKEY, NOISE_ROBUST_CAUCHY, NOISE_BASE_MASK = 1 << 4, 2 << 4, 3 << 4, 15
 ORDER_NATURAL, ORDER_MINDEGREE, ORDER_ND, ORDER_SCHUR, ORDER_SCHUR_ND = range(5)
+PRECOND_DUMMY, PRECOND_BLOCK_JACOBI = range(2)
+SOLVER_MULTIFRONTAL, SOLVER_PCG = range(2)
 
 STATE_DIM = {VAR_POSE2: 3, VAR_POSE3: 12, VAR_CAMERA: 17}
 TANGENT_DIM = {VAR_POSE2: 3, VAR_POSE3: 6, VAR_CAMERA: 9}
@@ -84,7 +86,21 @@ class LMResult(C.Structure):
         ("trace_len", C.c_int32), ("trace_cap", C.c_int32),
         ("trace_error", _p(C.c_double)), ("trace_lambda", _p(C.c_double)),
         ("trace_accepted", _p(C.c_int32)),
+        ("pcg_iterations", C.c_int32),   # written only by a handle whose linear solver is PCG
     ]
+
+
+class PCGParams(C.Structure):
+    """gsx_pcg_params: ConjugateGradientParameters (gtsam/linear/ConjugateGradientSolver.h:29-51) + the preconditioner."""
+    _fields_ = [
+        ("max_iterations", C.c_int32), ("min_iterations", C.c_int32), ("reset", C.c_int32),
+        ("epsilon_rel", C.c_double), ("epsilon_abs", C.c_double), ("preconditioner", C.c_int32),
+    ]
+
+
+class PCGStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("gamma_initial", C.c_double),
+                ("gamma_final", C.c_double), ("threshold", C.c_double)]
 
 
 class Stats(C.Structure):
@@ -98,7 +114,8 @@ class Stats(C.Structure):
         + [(n, C.c_int64) for n in ("n_linearize", "n_factorize", "n_backsolve", "n_error", "n_cheirality")]
         + [("amalgamation_relax", C.c_double), ("amalgamation_max_frontal_dim", C.c_int64),
            ("n_medium_fronts", C.c_int64), ("n_tree_fronts", C.c_int64), ("n_upper_levels", C.c_int64),
-           ("n_constraint_rows", C.c_int64), ("n_constrained_fronts", C.c_int64)]
+           ("n_constraint_rows", C.c_int64), ("n_constrained_fronts", C.c_int64),
+           ("n_pcg_iterations", C.c_int64), ("n_pcg_solves", C.c_int64)]
     )
 
     def as_dict(self):
@@ -362,7 +379,7 @@ class Backend:
         n = min(r.trace_len, r.trace_cap)
         return dict(initial_error=r.initial_error, final_error=r.final_error, final_lambda=r.final_lambda,
                     iterations=r.iterations, inner_iterations=r.inner_iterations,
-                    n_solve_failures=r.n_solve_failures,
+                    n_solve_failures=r.n_solve_failures, pcg_iterations=r.pcg_iterations,
                     trace_error=tr[0][:n].copy(), trace_lambda=tr[1][:n].copy(), trace_accepted=tr[2][:n].copy())
 
     def lm_optimize(self, params: LMParams, trace_cap=4096):

@@ -223,6 +223,25 @@ class ProductBackend(A.Backend):
                                          C.c_double(max_diagonal), C.byref(e0), C.byref(ed), C.byref(et)), "lm_trial")
         return e0.value, ed.value, et.value
 
+    # -- the iterative linear solver (include/gsx.h: gsx_solve_pcg / gsx_set_linear_solver) ---------------------------
+    def solve_pcg(self, lam=0.0, diagonal_damping=False, min_diagonal=1e-6, max_diagonal=1e32, params=None,
+                  want_delta=True):
+        """The damped solve by preconditioned conjugate gradients: (delta or None, stats dict)."""
+        prm = params if params is not None else pcg_params_default()
+        out = np.zeros(self.tangent_size) if want_delta else None
+        st_out, bad = A.PCGStats(), C.c_uint64(0)
+        ptr = out.ctypes.data_as(C.POINTER(C.c_double)) if want_delta else None
+        st = self._fn("solve_pcg")(self._h, C.c_double(lam), C.c_int32(int(diagonal_damping)), C.c_double(min_diagonal),
+                                   C.c_double(max_diagonal), C.byref(prm), ptr,
+                                   C.c_int64(self.tangent_size if want_delta else 0), C.byref(st_out), C.byref(bad))
+        self._check(st, "solve_pcg", key=bad.value)
+        return out, {k: getattr(st_out, k) for k, _ in A.PCGStats._fields_}
+
+    def set_linear_solver(self, kind: int, params=None):
+        """kind = A.SOLVER_MULTIFRONTAL or A.SOLVER_PCG (params: A.PCGParams, None = the defaults)."""
+        self._check(self._fn("set_linear_solver")(self._h, C.c_int32(kind), C.byref(params) if params is not None else None),
+                    "set_linear_solver")
+
     def stats(self) -> dict:
         s = A.Stats()
         self._check(self._fn("get_stats")(self._h, C.byref(s)), "get_stats")
@@ -241,6 +260,15 @@ class ProductBackend(A.Backend):
         ms, n = C.c_double(), C.c_int64()
         self._check(self._fn("kernel_time")(self._h, name.encode(), C.byref(ms), C.byref(n)), "kernel_time")
         return ms.value, n.value
+
+
+def pcg_params_default() -> A.PCGParams:
+    """gsx_pcg_params_default: ConjugateGradientParameters() with the block-Jacobi preconditioner."""
+    p = A.PCGParams()
+    f = load().gsx_pcg_params_default
+    f.restype = None
+    f(C.byref(p))
+    return p
 
 
 def _dataset_to_arrays(ds, meta) -> A.ProblemArrays:

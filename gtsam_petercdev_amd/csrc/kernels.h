@@ -393,4 +393,32 @@ void launch_begin_factorization(double* scalars, double lambda, DevStatus* statu
 void launch_dense_partial(double* a, int n, int nf, DevStatus* status, hipStream_t st);
 int max_dynamic_lds();
 
+// ---- preconditioned conjugate gradients on the linearized graph (pcg.hip) ------------------------------------------
+// The largest tangent dimension of a variable the PCG kernels take, with either preconditioner: pcg_build_blocks keeps a
+// d x d block per wave in LDS and gives each row of a Cholesky column step a lane, pcg_jty keeps d products per wave in
+// LDS and needs two terms' worth of lanes (G = 64 / d >= 2).  Typed variables have 3, 6 and 9; VECTOR(d) is the caller's.
+constexpr int kPcgMaxDim = 32;
+// Iterations the host enqueues between two reads of the done flag (7 launches each, 10 with a restart).
+#ifndef GSX_PCG_BATCH
+#define GSX_PCG_BATCH 8
+#endif
+constexpr int kPcgBatch = GSX_PCG_BATCH;
+static_assert(kPcgBatch >= 1, "GSX_PCG_BATCH must be at least 1");
+// the loop's scalars on the device (ConjugateGradientSolver.h:119-151), written by one thread of a one-workgroup kernel
+struct PcgScalars {
+  double gamma, gamma0, threshold, alpha, beta, pAp;
+  int k;         // iterations completed
+  int done;      // the reference's loop condition has failed (or fail != 0): every later kernel returns at once
+  int fail;      // 1: p'Ap non-positive or non-finite while gamma > threshold; 2: a diagonal block has no Cholesky factor
+  int bad_var;   // smallest variable whose block failed (INT_MAX: none)
+};
+struct HostProblem;
+struct PcgWork;   // device tables and vectors of one problem
+int pcg_max_dim(const HostProblem& P);
+hipError_t pcg_work_create(const HostProblem& P, hipStream_t st, PcgWork** out);
+void pcg_work_destroy(PcgWork* w);
+// x (device, tangent order) = the PCG estimate of (J'J + lambda diag(damp)) x = J'b; synchronises `st` once per batch
+hipError_t pcg_run(PcgWork* w, const double* jac, const double* damp, double lambda, const gsx_pcg_params& prm, double* x,
+                   DevStatus* status, hipStream_t st, PcgScalars* out);
+
 }  // namespace gsx

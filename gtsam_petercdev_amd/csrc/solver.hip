@@ -256,6 +256,14 @@ struct gsx_context {
   bool fact_pending = false; // a factorization is queued whose status the host has not read yet (readback decides)
   int damp_kind = -1;
   double damp_min = 0, damp_max = 0;
+  // the iterative linear solver (gsx_set_linear_solver / gsx_solve_pcg; pcg.hip): the tables and vectors are made on first
+  // use and dropped whenever the problem changes (upload_problem)
+  int solver_kind = GSX_SOLVER_MULTIFRONTAL;
+  gsx_pcg_params pcg_params{};
+  PcgWork* pcg = nullptr;
+  int64_t pcg_iterations = 0, pcg_solves = 0;   // since the last gsx_reset_stats
+  int64_t pcg_run_iterations = 0;               // of the driver call in progress
+  bool use_pcg() const { return solver_kind == GSX_SOLVER_PCG; }
   // LM state
   double lm_lambda = 0, lm_factor = 0, lm_error = 0;
   int lm_iterations = 0, lm_inner = 0;
@@ -413,6 +421,8 @@ void whiten_linear_factor(const HostProblem& P, int f, const double* src, double
 gsx_status upload_problem(gsx_context* c) {
   const HostProblem& P = c->P;
   hipStream_t st = c->stream;
+  pcg_work_destroy(c->pcg);
+  c->pcg = nullptr;
   HIPCHK(c, c->d_var_type.upload(P.types, st));
   HIPCHK(c, c->d_var_dim.upload(P.dims, st));
   HIPCHK(c, c->d_var_state_off.upload(P.state_off, st));
@@ -1626,7 +1636,7 @@ void dev_backsolve(gsx_context* c, const WildfireArgs* wf = nullptr) {
 void dev_linear_error(gsx_context* c, bool solved_step = false) {
   // (hard constraints: the step solves the KKT system, not (H + lambda D) delta = g — the identity below does not hold)
   static const bool direct_env = std::getenv("GSX_LINERR_DIRECT") != nullptr;
-  const bool direct_only = direct_env || c->constrained();
+  const bool direct_only = direct_env || c->constrained() || c->use_pcg();  // (PCG: the step is not exact either)
   timer_begin(c, PH_LINERR);
   if (solved_step && !direct_only && c->h_ready) {
     if (!c->lin0_ready) {
@@ -1699,6 +1709,64 @@ gsx_status need_device(gsx_context* c) {
   return GSX_OK;
 }
 
+// ---- the iterative linear solver (pcg.hip) -------------------------------------------------------------------------
+const char* pcg_params_error(const gsx_pcg_params& p) {
+  if (p.max_iterations < 0 || p.min_iterations < 0) return "PCG: negative iteration bound";
+  if (p.reset < 1) return "PCG: reset must be at least 1 (the reference takes k % reset)";
+  if (!(p.epsilon_rel >= 0.0) || !(p.epsilon_abs >= 0.0)) return "PCG: a negative or NaN epsilon";
+  if (p.preconditioner != GSX_PRECOND_DUMMY && p.preconditioner != GSX_PRECOND_BLOCK_JACOBI)
+    return "PCG: unknown preconditioner (the subgraph preconditioner is not offered)";
+  return nullptr;
+}
+// what keeps a handle from solving by PCG at all
+gsx_status pcg_refusal(gsx_context* c) {
+  if (c->sharded()) {
+    c->err = "the PCG solver is not available on a sharded handle";
+    return GSX_E_STATE;
+  }
+  if (!c->P.con_factor.empty()) {
+    c->err = "the PCG solver is not available on a problem with hard constraints (the step there is a KKT solve)";
+    return GSX_E_STATE;
+  }
+  return GSX_OK;
+}
+// (J'J + lambda D) delta = J'b by PCG into d_delta, D from the handle's damping vector (dev_damping first).  Synchronises.
+// GSX_E_INDETERMINATE leaves the handle usable (solved = false).
+gsx_status pcg_solve(gsx_context* c, double lambda, const gsx_pcg_params& prm, gsx_pcg_stats* stats, uint64_t* bad_key) {
+  gsx_status rs = pcg_refusal(c);   // (also here: gsx_update may have brought constraint rows in since the solver was chosen)
+  if (rs != GSX_OK) return rs;
+  if (pcg_max_dim(c->P) > kPcgMaxDim) {   // (pcg.hip: the per-wave LDS arrays and lane maps of both preconditioners' kernels)
+    c->err = "PCG takes variables of tangent dimension up to 32";
+    return GSX_E_INVALID;
+  }
+  if (!c->pcg) HIPCHK(c, pcg_work_create(c->P, c->stream, &c->pcg));
+  PcgScalars sc{};
+  HIPCHK(c, pcg_run(c->pcg, c->d_jac.p, c->d_damp.p, lambda, prm, c->d_delta.p, c->d_status.p, c->stream, &sc));
+  c->wf_delta_valid = false;   // d_delta no longer holds the direct solution a wildfire pass starts from
+  c->pcg_iterations += sc.k;
+  c->pcg_run_iterations += sc.k;
+  c->pcg_solves++;
+  if (stats) {
+    stats->iterations = sc.k;
+    stats->converged = sc.gamma <= sc.threshold ? 1 : 0;
+    stats->gamma_initial = sc.gamma0;
+    stats->gamma_final = sc.gamma;
+    stats->threshold = sc.threshold;
+  }
+  if (sc.fail) {
+    c->solved = false;
+    if (sc.fail == 2) {
+      if (bad_key && sc.bad_var >= 0 && sc.bad_var < c->P.n_vars) *bad_key = c->P.keys[sc.bad_var];
+      c->err = "indeterminate linear system: a diagonal block of the damped Hessian has no Cholesky factor";
+    } else {
+      c->err = "indeterminate linear system: p'Ap is not positive in the conjugate-gradient iteration";
+    }
+    return GSX_E_INDETERMINATE;
+  }
+  c->solved = true;
+  return GSX_OK;
+}
+
 // ---- LM policy (host scalars only) — LevenbergMarquardtOptimizer.cpp:121-308 ---------------------------
 struct Trace {
   gsx_lm_result* r;
@@ -1716,14 +1784,22 @@ struct Trace {
 // One damped trial on the device + the controller's verdict on it (csrc/lm_policy.cpp: gsx_lm_decide).
 gsx_status lm_try_lambda(gsx_context* c, const gsx_lm_params& p, Trace& tr, gsx_lm_result* res, bool* done) {
   dev_damping(c, p.diagonal_damping, p.min_diagonal, p.max_diagonal);
-  dev_factorize(c, c->lm_lambda);
-  dev_backsolve(c);
+  bool pcg_ok = true;
+  if (c->use_pcg()) {
+    gsx_status ps = pcg_solve(c, c->lm_lambda, c->pcg_params, nullptr, nullptr);
+    if (ps != GSX_OK && ps != GSX_E_INDETERMINATE) return ps;
+    pcg_ok = ps == GSX_OK;
+    if (!pcg_ok) hipMemsetAsync(c->d_delta.p, 0, (size_t)c->P.tan_size * sizeof(double), c->stream);  // (nothing to retract by)
+  } else {
+    dev_factorize(c, c->lm_lambda);
+    dev_backsolve(c);
+  }
   dev_linear_error(c, true);
   dev_retract(c, c->d_delta.p);
   dev_error(c, c->d_trial.p, SC_TRIAL_ERR);
   gsx_status st = readback(c);
   if (st != GSX_OK) return st;
-  const bool solved = factorization_ok(c);
+  const bool solved = c->use_pcg() ? pcg_ok : factorization_ok(c);
   if (!solved && res) res->n_solve_failures++;
   gsx_lm_state ctl{c->lm_lambda, c->lm_factor, c->lm_error, c->lm_iterations, c->lm_inner};
   gsx_lm_decision d;
@@ -1750,7 +1826,8 @@ gsx_status lm_try_lambda(gsx_context* c, const gsx_lm_params& p, Trace& tr, gsx_
 
 gsx_status lm_iterate(gsx_context* c, const gsx_lm_params& p, Trace& tr, gsx_lm_result* res) {
   dev_linearize(c);
-  dev_assemble_h(c);
+  // (a PCG handle reads H only for diag(J'J), the weights of diagonal damping)
+  if (!c->use_pcg() || p.diagonal_damping) dev_assemble_h(c);
   bool done = false;
   while (!done) {
     gsx_status st = lm_try_lambda(c, p, tr, res, &done);
@@ -1853,6 +1930,8 @@ gsx_status gsx_destroy(gsx_handle h) {
     }
     if (h->h_scalars) hipHostFree(h->h_scalars);
     if (h->h_status) hipHostFree(h->h_status);
+    pcg_work_destroy(h->pcg);
+    h->pcg = nullptr;
   }
   hipStream_t st = h->stream;
   const bool dev = h->has_device;
@@ -1911,6 +1990,10 @@ gsx_status gsx_set_shard(gsx_handle h, int32_t rank, int32_t world, gsx_allreduc
   if (!h || world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce)) return GSX_E_INVALID;
   if (h->has_symbolic) {
     h->err = "gsx_set_shard must precede gsx_set_ordering";
+    return GSX_E_STATE;
+  }
+  if (world > 1 && h->use_pcg()) {
+    h->err = "the PCG solver is not available on a sharded handle";
     return GSX_E_STATE;
   }
   h->shard_rank = rank;
@@ -2133,6 +2216,60 @@ gsx_status gsx_solve(gsx_handle h, double lambda, int32_t diagonal_damping, doub
   return GSX_OK;
 }
 
+void gsx_pcg_params_default(gsx_pcg_params* p) {
+  // ConjugateGradientParameters() — gtsam/linear/ConjugateGradientSolver.h:45-51: minIterations 1, maxIterations 500,
+  // reset 501, epsilon_rel 1e-3, epsilon_abs 1e-3
+  if (p) *p = gsx_pcg_params{500, 1, 501, 1e-3, 1e-3, GSX_PRECOND_BLOCK_JACOBI};
+}
+
+gsx_status gsx_set_linear_solver(gsx_handle h, int32_t kind, const gsx_pcg_params* params) {
+  if (!h || (kind != GSX_SOLVER_MULTIFRONTAL && kind != GSX_SOLVER_PCG)) return GSX_E_INVALID;
+  if (kind == GSX_SOLVER_MULTIFRONTAL) {
+    h->solver_kind = kind;
+    return GSX_OK;
+  }
+  gsx_pcg_params prm;
+  gsx_pcg_params_default(&prm);
+  if (params) prm = *params;
+  if (const char* what = pcg_params_error(prm)) {
+    h->err = what;
+    return GSX_E_INVALID;
+  }
+  gsx_status st = pcg_refusal(h);
+  if (st != GSX_OK) return st;
+  h->solver_kind = kind;
+  h->pcg_params = prm;
+  return GSX_OK;
+}
+
+gsx_status gsx_solve_pcg(gsx_handle h, double lambda, int32_t diagonal_damping, double min_diagonal, double max_diagonal,
+                         const gsx_pcg_params* params, double* delta_out, int64_t n, gsx_pcg_stats* stats_out,
+                         uint64_t* bad_key) {
+  if (!h || !params || !(lambda >= 0.0) || (delta_out && n != h->P.tan_size)) return GSX_E_INVALID;
+  if (const char* what = pcg_params_error(*params)) {
+    h->err = what;
+    return GSX_E_INVALID;
+  }
+  gsx_status st = ensure_ready(h, true, diagonal_damping != 0);
+  if (st != GSX_OK) return st;
+  st = pcg_refusal(h);
+  if (st != GSX_OK) return st;
+  if (!h->linearized) {
+    h->err = "linearize first";
+    return GSX_E_STATE;
+  }
+  hipSetDevice(h->device);
+  if (diagonal_damping && !h->h_ready) dev_assemble_h(h);   // diag(J'J) is read from the H panels
+  dev_damping(h, diagonal_damping, min_diagonal, max_diagonal);
+  st = pcg_solve(h, lambda, *params, stats_out, bad_key);
+  if (st != GSX_OK) return st;
+  if (delta_out && n > 0) {
+    HIPCHK(h, hipMemcpyAsync(delta_out, h->d_delta.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return GSX_OK;
+}
+
 // ISAM2's partial ("wildfire") back-substitution (include/gsx.h; gtsam/nonlinear/ISAM2-impl.cpp:48-77,
 // ISAM2Clique.cpp:203-287) on the resident undamped factorization.
 gsx_status gsx_backsubstitute_wildfire(gsx_handle h, double threshold, double* delta_out, int64_t n,
@@ -2284,16 +2421,23 @@ gsx_status gsx_lm_trial(gsx_handle h, int32_t relinearize, double lambda, int32_
   }
   hipSetDevice(h->device);
   if (relinearize) dev_linearize(h);
-  if (!h->h_ready) dev_assemble_h(h);
-  dev_damping(h, diagonal_damping, min_diagonal, max_diagonal);
-  dev_factorize(h, lambda);
-  dev_backsolve(h);
+  if (h->use_pcg()) {
+    if (diagonal_damping && !h->h_ready) dev_assemble_h(h);
+    dev_damping(h, diagonal_damping, min_diagonal, max_diagonal);
+    st = pcg_solve(h, lambda, h->pcg_params, nullptr, nullptr);
+    if (st != GSX_OK) return st;
+  } else {
+    if (!h->h_ready) dev_assemble_h(h);
+    dev_damping(h, diagonal_damping, min_diagonal, max_diagonal);
+    dev_factorize(h, lambda);
+    dev_backsolve(h);
+  }
   dev_linear_error(h, true);
   dev_retract(h, h->d_delta.p);
   dev_error(h, h->d_trial.p, SC_TRIAL_ERR);
   st = readback(h);
   if (st != GSX_OK) return st;
-  if (h->h_status->n_fail > 0 || h->h_status->n_nonfinite > 0) {
+  if (!h->use_pcg() && (h->h_status->n_fail > 0 || h->h_status->n_nonfinite > 0)) {
     h->solved = false;
     h->fact_valid = false;
     h->err = "indeterminate linear system";
@@ -2319,6 +2463,7 @@ gsx_status gsx_lm_optimize(gsx_handle h, const gsx_lm_params* p, gsx_lm_result* 
     r->trace_len = 0;
     r->n_solve_failures = 0;
   }
+  h->pcg_run_iterations = 0;
   double currentError = h->lm_error;
   if (!(currentError <= p->error_tol) && !(h->lm_iterations >= p->max_iterations)) {
     double newError = currentError;
@@ -2336,6 +2481,7 @@ gsx_status gsx_lm_optimize(gsx_handle h, const gsx_lm_params* p, gsx_lm_result* 
     r->final_lambda = h->lm_lambda;
     r->iterations = h->lm_iterations;
     r->inner_iterations = h->lm_inner;
+    if (h->use_pcg()) r->pcg_iterations = (int32_t)h->pcg_run_iterations;
   }
   return GSX_OK;
 }
@@ -2350,6 +2496,7 @@ gsx_status gsx_gn_optimize(gsx_handle h, int32_t max_iterations, double relTol, 
   st = compute_error_sync(h, &h->lm_error);
   if (st != GSX_OK) return st;
   h->lm_iterations = 0;
+  h->pcg_run_iterations = 0;
   Trace tr{r};
   if (r) {
     r->initial_error = h->lm_error;
@@ -2362,15 +2509,21 @@ gsx_status gsx_gn_optimize(gsx_handle h, int32_t max_iterations, double relTol, 
     do {
       currentError = newError;
       dev_linearize(h);
-      dev_assemble_h(h);
-      dev_damping(h, 0, 0, 0);
-      dev_factorize(h, 0.0);
-      dev_backsolve(h);
+      if (h->use_pcg()) {   // PCGSolver on the undamped graph (NonlinearOptimizer.cpp:154-162 from GaussNewtonOptimizer::iterate)
+        dev_damping(h, 0, 0, 0);
+        st = pcg_solve(h, 0.0, h->pcg_params, nullptr, nullptr);
+        if (st != GSX_OK) return st;
+      } else {
+        dev_assemble_h(h);
+        dev_damping(h, 0, 0, 0);
+        dev_factorize(h, 0.0);
+        dev_backsolve(h);
+      }
       dev_retract(h, h->d_delta.p);
       dev_error(h, h->d_trial.p, SC_TRIAL_ERR);
       st = readback(h);
       if (st != GSX_OK) return st;
-      if (h->h_status->n_fail > 0 || h->h_status->n_nonfinite > 0) {
+      if (!h->use_pcg() && (h->h_status->n_fail > 0 || h->h_status->n_nonfinite > 0)) {
         h->err = "indeterminate linear system";
         return GSX_E_INDETERMINATE;
       }
@@ -2389,6 +2542,7 @@ gsx_status gsx_gn_optimize(gsx_handle h, int32_t max_iterations, double relTol, 
     r->final_lambda = 0;
     r->iterations = h->lm_iterations;
     r->inner_iterations = h->lm_iterations;
+    if (h->use_pcg()) r->pcg_iterations = (int32_t)h->pcg_run_iterations;
   }
   return GSX_OK;
 }
@@ -2443,6 +2597,11 @@ gsx_status gsx_dogleg_optimize(gsx_handle h, double delta_initial, int32_t max_i
   if (h->constrained()) {
     // (the steepest-descent leg of the dog leg knows nothing of the constraint rows: a blended step would violate them)
     h->err = "Dogleg is not available on a problem with hard constraints";
+    return GSX_E_STATE;
+  }
+  if (h->use_pcg()) {
+    // (the dog leg blends the steepest-descent point with the EXACT Gauss-Newton point of the Bayes tree)
+    h->err = "Dogleg is not available on a handle whose linear solver is PCG";
     return GSX_E_STATE;
   }
   hipSetDevice(h->device);
@@ -3680,6 +3839,8 @@ gsx_status gsx_get_stats(gsx_handle h, gsx_stats* out) {
   out->n_backsolve = h->timers[PH_BACKSOLVE].count;
   out->n_error = h->timers[PH_ERROR].count;
   out->n_cheirality = h->n_cheirality;
+  out->n_pcg_iterations = h->pcg_iterations;
+  out->n_pcg_solves = h->pcg_solves;
   out->amalgamation_relax = h->S.relax;
   out->amalgamation_max_frontal_dim = h->S.relax_max_f;
   return GSX_OK;
@@ -3695,6 +3856,7 @@ gsx_status gsx_reset_stats(gsx_handle h) {
     t.ms = 0;
     t.count = 0;
   }
+  h->pcg_iterations = h->pcg_solves = 0;
   return GSX_OK;
 }
 

@@ -722,6 +722,59 @@ def _make_backend(arrays, backend_factory):
 
 
 # ---- optimizers ---------------------------------------------------------------------------------
+class DummyPreconditionerParameters:
+    """gtsam/linear/Preconditioner.h: the identity."""
+    kind = A.PRECOND_DUMMY
+
+
+class BlockJacobiPreconditionerParameters:
+    """gtsam/linear/Preconditioner.h: Cholesky factors of the diagonal blocks of the damped Hessian."""
+    kind = A.PRECOND_BLOCK_JACOBI
+
+
+class PCGSolverParameters:
+    """gtsam/linear/PCGSolver.h:36-50 over ConjugateGradientParameters (ConjugateGradientSolver.h:29-96), with its
+    setter names.  The subgraph preconditioner is not offered by the backend."""
+
+    def __init__(self, preconditioner=None):
+        self.minIterations, self.maxIterations, self.reset = 1, 500, 501
+        self.epsilon_rel, self.epsilon_abs = 1e-3, 1e-3
+        self.preconditioner = preconditioner if preconditioner is not None else BlockJacobiPreconditionerParameters()
+
+    def setMinIterations(self, v): self.minIterations = int(v)
+    def setMaxIterations(self, v): self.maxIterations = int(v)
+    def setReset(self, v): self.reset = int(v)
+    def setEpsilon(self, v): self.epsilon_rel = float(v)
+    def setEpsilon_rel(self, v): self.epsilon_rel = float(v)
+    def setEpsilon_abs(self, v): self.epsilon_abs = float(v)
+    def setPreconditionerParams(self, p): self.preconditioner = p
+
+    def c_params(self) -> A.PCGParams:
+        return A.PCGParams(int(self.maxIterations), int(self.minIterations), int(self.reset), float(self.epsilon_rel),
+                           float(self.epsilon_abs), int(self.preconditioner.kind))
+
+
+def _route_linear_solver(backend, linearSolverType, iterativeParams):
+    """NonlinearOptimizerParams::linearSolverType (NonlinearOptimizerParams.h:81-108): "ITERATIVE" with
+    PCGSolverParameters goes to gsx_set_linear_solver; the direct kinds all mean the multifrontal Cholesky here."""
+    if str(linearSolverType).upper() == "ITERATIVE":
+        if not isinstance(iterativeParams, PCGSolverParameters):
+            raise ValueError("linearSolverType ITERATIVE needs iterativeParams = PCGSolverParameters (the subgraph "
+                             "solver is not offered)")
+        backend.set_linear_solver(A.SOLVER_PCG, iterativeParams.c_params())
+
+
+class GaussNewtonParams:
+    """gtsam/nonlinear/GaussNewtonParams.h = NonlinearOptimizerParams (NonlinearOptimizerParams.h:42-108)."""
+
+    def __init__(self):
+        self.maxIterations, self.relativeErrorTol, self.absoluteErrorTol, self.errorTol = 100, 1e-5, 1e-5, 0.0
+        self.ordering: Optional[Ordering] = None
+        self.orderingType = "COLAMD"
+        self.linearSolverType = "MULTIFRONTAL_CHOLESKY"
+        self.iterativeParams = None
+
+
 class LevenbergMarquardtParams:
     """gtsam/nonlinear/LevenbergMarquardtParams.h:61-98 + NonlinearOptimizerParams.h:42-108."""
     SILENT, SUMMARY = 0, 1
@@ -731,6 +784,8 @@ class LevenbergMarquardtParams:
         # the class default lambdaInitial/lambdaFactor etc. ARE the legacy values;
         self.ordering: Optional[Ordering] = None
         self.orderingType = "COLAMD"
+        self.linearSolverType = "MULTIFRONTAL_CHOLESKY"   # or "ITERATIVE" with iterativeParams = PCGSolverParameters
+        self.iterativeParams = None
 
     def _set(self, p: A.LMParams):
         self.maxIterations, self.relativeErrorTol = p.max_iterations, p.relative_error_tol
@@ -804,6 +859,7 @@ class LevenbergMarquardtOptimizer(_OptimizerBase):
             ordering = params.ordering
         self.params_ = params
         super().__init__(graph, initialValues, ordering, params.orderingType, backend_factory, ordering_fn)
+        _route_linear_solver(self.backend, params.linearSolverType, params.iterativeParams)
         self.backend.lm_reset(params.c_params())
         self._iterations = 0
         self._lambda = params.lambdaInitial
@@ -841,8 +897,15 @@ class DoglegOptimizer(_OptimizerBase):
 
 class GaussNewtonOptimizer(_OptimizerBase):
     def __init__(self, graph, initialValues, ordering=None, maxIterations=100, relativeErrorTol=1e-5,
-                 absoluteErrorTol=1e-5, errorTol=0.0, backend_factory=None, ordering_fn=None, orderingType="COLAMD"):
+                 absoluteErrorTol=1e-5, errorTol=0.0, backend_factory=None, ordering_fn=None, orderingType="COLAMD",
+                 params: Optional["GaussNewtonParams"] = None):
+        if params is not None:   # GaussNewtonOptimizer(graph, initialValues, params)
+            maxIterations, relativeErrorTol = params.maxIterations, params.relativeErrorTol
+            absoluteErrorTol, errorTol, orderingType = params.absoluteErrorTol, params.errorTol, params.orderingType
+            ordering = ordering if ordering is not None else params.ordering
         super().__init__(graph, initialValues, ordering, orderingType, backend_factory, ordering_fn)
+        if params is not None:
+            _route_linear_solver(self.backend, params.linearSolverType, params.iterativeParams)
         self._p = (maxIterations, relativeErrorTol, absoluteErrorTol, errorTol)
         self._iterations = 0
 

@@ -276,6 +276,8 @@ typedef struct gsx_lm_result {
   double* trace_error;           /* error after the inner iteration            */
   double* trace_lambda;          /* lambda tried                               */
   int32_t* trace_accepted;       /* 1 accepted, 0 rejected, -1 solve failed    */
+  int32_t pcg_iterations;        /* PCG iterations of all solves of the run; written ONLY by a handle whose linear
+                                    solver is GSX_SOLVER_PCG (callers built before the field existed never set one) */
 } gsx_lm_result;
 
 /* Symbolic-analysis and timing counters (gsx_get_stats). */
@@ -306,6 +308,8 @@ typedef struct gsx_stats {
   int64_t n_upper_levels;        /* launch rounds of the fronts that are neither: levelled among themselves (longest chain) */
   int64_t n_constraint_rows;     /* hard-constraint (zero-sigma) rows of the graph */
   int64_t n_constrained_fronts;  /* fronts that take constraint rows in (always blocked; constraint pivots before Cholesky) */
+  int64_t n_pcg_iterations;      /* PCG iterations since the last gsx_reset_stats (gsx_solve_pcg and the drivers of a PCG handle) */
+  int64_t n_pcg_solves;          /* ... and the solves they belong to */
 } gsx_stats;
 
 /* ---- on-disk formats (host only) -------------------------
@@ -611,6 +615,57 @@ gsx_status gsx_set_block_jacobians(gsx_handle h, int32_t first_factor, int32_t n
  * queries the sizes. */
 gsx_status gsx_get_conditional(gsx_handle h, int32_t front, int32_t* n_frontal, int32_t* n_cols, double* out,
                                int64_t n_out);
+
+/* ---- the iterative linear solver: NonlinearOptimizerParams::linearSolverType = Iterative with PCGSolverParameters ------
+ * (gtsam/nonlinear/NonlinearOptimizer.cpp:154-162: PCGSolver(*pcg).optimize(gfg) on the damped graph.)
+ * preconditionedConjugateGradient (gtsam/linear/ConjugateGradientSolver.h:109-171) on the device for
+ * A = J'J + lambda D, b = J'b, initial estimate zero, matrix-free over the [A b] blocks (csrc/pcg.hip), with
+ * BlockJacobiPreconditioner (gtsam/linear/Preconditioner.cpp:87-176) or DummyPreconditioner (the identity).  The
+ * subgraph preconditioner and SubgraphSolver are not offered.  A variable's tangent dimension may be at most 32, with
+ * either preconditioner (GSX_E_INVALID from the solve beyond).
+ * The loop is the reference's, condition for condition:
+ *   for (k = 1; k <= max_iterations && (gamma > threshold || k <= min_iterations); k++), threshold =
+ *   max(epsilon_abs, epsilon_rel^2 gamma_0), and at k % reset == 0 a restart from the true residual (reset >= 1).
+ * gsx_pcg_stats.iterations counts the loop bodies executed: gamma after `iterations` bodies is gamma_final (the
+ * reference's own counter stands one higher when its loop ends).  converged = gamma_final <= threshold; running into
+ * max_iterations is not an error — the estimate is returned with converged = 0, as the reference returns it.
+ * GSX_E_INDETERMINATE: a diagonal block has no Cholesky factor (*bad_key = its variable), or p'Ap is non-positive or
+ * non-finite while gamma > threshold (*bad_key untouched).
+ * gamma_0 = 0 (linearized at a stationary point) is NOT special-cased, because the reference does not: with
+ * min_iterations >= 1 the first body computes alpha = 0 / 0, and the estimate returned is all NaN, status GSX_OK,
+ * gamma_final NaN, converged 0; with min_iterations = 0 no body runs and the estimate is zero. */
+enum { GSX_PRECOND_DUMMY = 0, GSX_PRECOND_BLOCK_JACOBI = 1 };
+enum { GSX_SOLVER_MULTIFRONTAL = 0, GSX_SOLVER_PCG = 1 };
+typedef struct gsx_pcg_params {
+  int32_t max_iterations;        /* 500   ConjugateGradientSolver.h:47                                   */
+  int32_t min_iterations;        /* 1     :46                                                            */
+  int32_t reset;                 /* 501   :48                                                            */
+  double epsilon_rel;            /* 1e-3  :49                                                            */
+  double epsilon_abs;            /* 1e-3  :50                                                            */
+  int32_t preconditioner;        /* GSX_PRECOND_*: the reference's PCGSolverParameters has no default
+                                    (a null pointer); the default here is GSX_PRECOND_BLOCK_JACOBI     */
+} gsx_pcg_params;
+typedef struct gsx_pcg_stats {
+  int32_t iterations;            /* loop bodies executed                                                 */
+  int32_t converged;             /* gamma_final <= threshold                                             */
+  double gamma_initial, gamma_final, threshold;
+} gsx_pcg_stats;
+void gsx_pcg_params_default(gsx_pcg_params* p);
+/* The damped solve of gsx_solve by PCG on a linearized handle; D = I or clamp(diag J'J, min_diagonal, max_diagonal)
+ * as there.  Builds no fronts and leaves the factorization arena alone.  delta_out (may be NULL), stats_out (may be
+ * NULL), bad_key (may be NULL); delta stays on the device for gsx_retract / gsx_linear_error.  GSX_E_STATE: not
+ * linearized, sharded handle, hard constraints (the step there is a KKT solve). */
+gsx_status gsx_solve_pcg(gsx_handle h, double lambda, int32_t diagonal_damping, double min_diagonal, double max_diagonal,
+                         const gsx_pcg_params* params, double* delta_out, int64_t n, gsx_pcg_stats* stats_out,
+                         uint64_t* bad_key);
+/* Which linear solver gsx_lm_optimize / gsx_lm_iterate / gsx_lm_trial / gsx_gn_optimize take their step from.  kind =
+ * GSX_SOLVER_MULTIFRONTAL (the default of a new handle; params ignored) or GSX_SOLVER_PCG (params = NULL: the defaults).
+ * A PCG handle evaluates the two linearized errors of a trial directly on [A b] (the model-decrease identity holds for an
+ * exact solve only), adds the iterations of every solve into gsx_lm_result.pcg_iterations / gsx_stats.n_pcg_iterations,
+ * and treats GSX_E_INDETERMINATE from the solve like a failed factorization.  GSX_E_STATE: PCG on a sharded handle or on
+ * a problem with hard constraints; gsx_dogleg_optimize on a PCG handle.  The marginal and conditional queries need the
+ * direct factorization exactly as before, whatever the solver kind. */
+gsx_status gsx_set_linear_solver(gsx_handle h, int32_t kind, const gsx_pcg_params* params);
 
 /* ---- the linear seam (NonlinearOptimizer::solve override) ------------------- */
 /* desc must contain only GSX_F_LINEAR factors and GSX_VAR_VECTOR variables;

@@ -30,6 +30,8 @@
 #include <gtsam/linear/GaussianFactorGraph.h>
 #include <gtsam/linear/JacobianFactor.h>
 #include <gtsam/linear/NoiseModel.h>
+#include <gtsam/linear/PCGSolver.h>
+#include <gtsam/linear/Preconditioner.h>
 #include <gtsam/linear/VectorValues.h>
 #include <gtsam/linear/linearExceptions.h>
 #include <gtsam/nonlinear/LevenbergMarquardtOptimizer.h>
@@ -328,6 +330,12 @@ class GsxLevenbergMarquardtOptimizer : public gtsam::LevenbergMarquardtOptimizer
   // ---- L2: the whole run on the device -------------------------------------------------------------------------------------
   const gtsam::Values& optimize() override {
     using namespace gtsam;
+    // NonlinearOptimizer::solve's Iterative branch (gtsam/nonlinear/NonlinearOptimizer.cpp:154-162): PCGSolverParameters
+    // with the block-Jacobi or the dummy preconditioner is the device PCG solve; every other iterative solver
+    // (SubgraphSolverParameters, the subgraph preconditioner) stays with the reference's own optimizer
+    gsx_pcg_params pcg;
+    const bool use_pcg = params().isIterative();
+    if (use_pcg && !lower_pcg(params(), &pcg)) return LevenbergMarquardtOptimizer::optimize();
     Lowered L;
     std::vector<double> packed;
     lower_values(values(), L, packed);
@@ -355,6 +363,7 @@ class GsxLevenbergMarquardtOptimizer : public gtsam::LevenbergMarquardtOptimizer
     const Ordering ordering = params().ordering ? *params().ordering : Ordering::Create(params().orderingType, g);
     const std::vector<uint64_t> ord(ordering.begin(), ordering.end());
     check(gsx_set_ordering(h, ord.data(), (int32_t)ord.size()), h, "gsx_set_ordering");
+    if (use_pcg) check(gsx_set_linear_solver(h, GSX_SOLVER_PCG, &pcg), h, "gsx_set_linear_solver");
     const gsx_lm_params p = lower_params(params());
     double final_error = 0, final_lambda = 0;
     int iterations = 0, inner = 0;
@@ -363,7 +372,7 @@ class GsxLevenbergMarquardtOptimizer : public gtsam::LevenbergMarquardtOptimizer
       check(gsx_lm_optimize(h, &p, &r), h, "gsx_lm_optimize");
       final_error = r.final_error, final_lambda = r.final_lambda, iterations = r.iterations, inner = r.inner_iterations;
     } else {
-      run_with_fallback(h, L, p, packed, final_error, final_lambda, iterations, inner);
+      run_with_fallback(h, L, p, use_pcg ? &pcg : nullptr, packed, final_error, final_lambda, iterations, inner);
     }
     check(gsx_get_values(h, packed.data(), (int64_t)packed.size()), h, "gsx_get_values");
     state_.reset(new internal::LevenbergMarquardtState(unpack_values(values(), packed), final_error, final_lambda,
@@ -374,7 +383,29 @@ class GsxLevenbergMarquardtOptimizer : public gtsam::LevenbergMarquardtOptimizer
  private:
   // the trial loop of LevenbergMarquardtOptimizer::iterate / tryLambda with the CPU-linearized slots refreshed per
   // linearization point and their nonlinear error added on the host; decisions by gsx_lm_decide
-  void run_with_fallback(gsx_handle h, const Lowered& L, const gsx_lm_params& p, std::vector<double>& packed, double& final_error,
+  // PCGSolverParameters -> gsx_pcg_params; false for what the device solver does not offer
+  static bool lower_pcg(const gtsam::LevenbergMarquardtParams& params, gsx_pcg_params* q) {
+    using namespace gtsam;
+    const auto pcg = std::dynamic_pointer_cast<PCGSolverParameters>(params.iterativeParams);
+    if (!pcg) return false;
+    gsx_pcg_params_default(q);
+    q->max_iterations = (int32_t)pcg->maxIterations;
+    q->min_iterations = (int32_t)pcg->minIterations;
+    q->reset = (int32_t)pcg->reset;
+    q->epsilon_rel = pcg->epsilon_rel;
+    q->epsilon_abs = pcg->epsilon_abs;
+    if (std::dynamic_pointer_cast<BlockJacobiPreconditionerParameters>(pcg->preconditioner))
+      q->preconditioner = GSX_PRECOND_BLOCK_JACOBI;
+    else if (std::dynamic_pointer_cast<DummyPreconditionerParameters>(pcg->preconditioner))
+      q->preconditioner = GSX_PRECOND_DUMMY;
+    else
+      return false;
+    return true;
+  }
+
+  // (pcg != nullptr: the damped solve of a trial is gsx_solve_pcg)
+  void run_with_fallback(gsx_handle h, const Lowered& L, const gsx_lm_params& p, const gsx_pcg_params* pcg,
+                         std::vector<double>& packed, double& final_error,
                          double& final_lambda, int& iterations, int& inner) {
     using namespace gtsam;
     const NonlinearFactorGraph& g = graph();
@@ -402,8 +433,11 @@ class GsxLevenbergMarquardtOptimizer : public gtsam::LevenbergMarquardtOptimizer
       gsx_lm_decision dec{};
       do {
         uint64_t bad = 0;
-        const gsx_status s = gsx_solve(h, st.lambda, p.diagonal_damping, p.min_diagonal, p.max_diagonal, delta.data(),
-                                       (int64_t)delta.size(), &bad);
+        const gsx_status s =
+            pcg ? gsx_solve_pcg(h, st.lambda, p.diagonal_damping, p.min_diagonal, p.max_diagonal, pcg, delta.data(),
+                                (int64_t)delta.size(), nullptr, &bad)
+                : gsx_solve(h, st.lambda, p.diagonal_damping, p.min_diagonal, p.max_diagonal, delta.data(),
+                            (int64_t)delta.size(), &bad);
         double lin0 = 0, lind = 0, trial = 0;
         Values trial_values;
         if (s == GSX_OK) {
