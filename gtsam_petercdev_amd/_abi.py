@@ -122,6 +122,15 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class InitPose3Params(C.Structure):
+    """gsx_init_pose3_params: the arguments of InitializePose3::initialize / computeOrientationsGradient / computePoses."""
+    _fields_ = [("use_gradient", C.c_int32), ("max_gradient_iterations", C.c_int32), ("set_ref_frame", C.c_int32),
+                ("single_iter", C.c_int32)]
+
+
+ANCHOR_KEY = 99999999   # initialize::kAnchorKey (gtsam/slam/InitializePose.h:30)
+
+
 def lm_params_legacy() -> LMParams:
     """LevenbergMarquardtParams::SetLegacyDefaults (LevenbergMarquardtParams.h:69-82)."""
     return LMParams(100, 1e-5, 1e-5, 0.0, 1e-5, 10.0, 1e5, 0.0, 1e-3, 0, 1, 1e-6, 1e32, 0)

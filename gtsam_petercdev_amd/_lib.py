@@ -396,5 +396,117 @@ def dogleg_point(delta: float, dx_u, dx_n) -> np.ndarray:
     return out
 
 
+# ---- Pose3 initialization (include/gsx.h: InitializePose3) -----------------------------------------------------------
+def _raise_init(st, what):
+    if st == A.GSX_E_INDETERMINATE:
+        raise A.IndeterminantLinearSystemException(None, what)
+    if st != A.GSX_OK:
+        raise A.GsxError(st, what, "")
+
+
+def _n_pose3(arrays) -> int:
+    return int(np.count_nonzero(arrays.var_types == A.VAR_POSE3))
+
+
+def init_pose3_params_default() -> A.InitPose3Params:
+    p = A.InitPose3Params()
+    f = load().gsx_init_pose3_params_default
+    f.restype = None
+    f(C.byref(p))
+    return p
+
+
+def initialize_pose3(arrays: A.ProblemArrays, given=None, params: A.InitPose3Params = None, device: int = 0):
+    """gsx_initialize_pose3: (packed Values of `arrays`, gradient iterations executed)."""
+    f = load().gsx_initialize_pose3
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    out = np.zeros(int(arrays.state_offsets()[-1]))
+    it = C.c_int32(0)
+    g = None if given is None else np.ascontiguousarray(given, dtype=np.float64)
+    st = f(C.byref(desc), None if g is None else A._dptr(g), C.c_int64(0 if g is None else g.size),
+           None if params is None else C.byref(params), C.c_int32(device), A._dptr(out), C.c_int64(out.size), C.byref(it))
+    _raise_init(st, "gsx_initialize_pose3")
+    return out, int(it.value)
+
+
+def pose3_orientations_chordal(arrays: A.ProblemArrays, device: int = 0) -> np.ndarray:
+    """gsx_pose3_orientations_chordal: (P, 3, 3) rotations of the POSE3 variables, in the order of `arrays`."""
+    f = load().gsx_pose3_orientations_chordal
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    out = np.zeros(9 * _n_pose3(arrays))
+    _raise_init(f(C.byref(desc), C.c_int32(device), A._dptr(out), C.c_int64(out.size)), "gsx_pose3_orientations_chordal")
+    return out.reshape(-1, 3, 3)
+
+
+def pose3_orientations_gradient(arrays: A.ProblemArrays, given, max_iter: int = 10000, set_ref_frame: bool = True,
+                                device: int = 0):
+    """gsx_pose3_orientations_gradient: ((P, 3, 3) rotations, iterations executed)."""
+    f = load().gsx_pose3_orientations_gradient
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    g = None if given is None else np.ascontiguousarray(given, dtype=np.float64)
+    out = np.zeros(9 * _n_pose3(arrays))
+    it = C.c_int32(0)
+    st = f(C.byref(desc), None if g is None else A._dptr(g), C.c_int64(0 if g is None else g.size), C.c_int32(max_iter),
+           C.c_int32(int(set_ref_frame)), C.c_int32(device), A._dptr(out), C.c_int64(out.size), C.byref(it))
+    _raise_init(st, "gsx_pose3_orientations_gradient")
+    return out.reshape(-1, 3, 3), int(it.value)
+
+
+def pose3_compute_poses(arrays: A.ProblemArrays, rot, single_iter: bool = True, fill=None, device: int = 0) -> np.ndarray:
+    """gsx_pose3_compute_poses: packed Values of `arrays`; what the pose graph does not hold keeps the entries of `fill`."""
+    f = load().gsx_pose3_compute_poses
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    r = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1)
+    n = int(arrays.state_offsets()[-1])
+    out = np.zeros(n) if fill is None else np.array(fill, dtype=np.float64).reshape(-1).copy()
+    st = f(C.byref(desc), A._dptr(r), C.c_int64(r.size), C.c_int32(int(single_iter)), C.c_int32(device), A._dptr(out),
+           C.c_int64(out.size))
+    _raise_init(st, "gsx_pose3_compute_poses")
+    return out
+
+
+def closest_rotations(m, device: int = 0) -> np.ndarray:
+    """gsx_closest_rotations: Rot3::ClosestTo of every 3 x 3 matrix of `m` (n, 3, 3)."""
+    f = load().gsx_closest_rotations
+    f.restype = C.c_int32
+    a = np.ascontiguousarray(m, dtype=np.float64).reshape(-1, 9)
+    out = np.zeros_like(a)
+    _raise_init(f(A._dptr(a), C.c_int64(a.shape[0]), C.c_int32(device), A._dptr(out)), "gsx_closest_rotations")
+    return out.reshape(-1, 3, 3)
+
+
+INIT_TIMING_NAMES = ("relaxed_analysis_host_ms", "chordal_blocks_ms", "three_relaxed_solves_ms", "projection_ms",
+                     "anchor_analysis_host_ms", "gauss_newton_ms", "gradient_ms", "gradient_iterations")
+
+
+def pose3_init_timings() -> dict:
+    """gsx_pose3_init_timings: the stage times of the last initializer call of the process."""
+    f = load().gsx_pose3_init_timings
+    f.restype = C.c_int32
+    out = np.zeros(len(INIT_TIMING_NAMES))
+    _raise_init(f(A._dptr(out), C.c_int32(out.size)), "gsx_pose3_init_timings")
+    return dict(zip(INIT_TIMING_NAMES, (float(x) for x in out)))
+
+
+def pose3_init_structure(arrays: A.ProblemArrays):
+    """gsx_pose3_init_structure (host): (edge_from, edge_to, adjacency lists per node); node P = the anchor."""
+    f = load().gsx_pose3_init_structure
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    ne = C.c_int32(0)
+    _raise_init(f(C.byref(desc), C.byref(ne), None, None, None, None, C.c_int64(0)), "gsx_pose3_init_structure")
+    n = ne.value
+    P = _n_pose3(arrays)
+    ef, et = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    ap, adj = np.zeros(P + 2, np.int32), np.zeros(max(2 * n, 1), np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _raise_init(f(C.byref(desc), C.byref(ne), ip(ef), ip(et), ip(ap), ip(adj), C.c_int64(2 * n)), "gsx_pose3_init_structure")
+    return ef[:n], et[:n], [adj[ap[i]:ap[i + 1]].tolist() for i in range(P + 1)]
+
+
 def product_backend(arrays: A.ProblemArrays, device: int = 0) -> ProductBackend:
     return ProductBackend(arrays, device)

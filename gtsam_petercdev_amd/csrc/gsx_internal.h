@@ -6,6 +6,8 @@
 
 #include "../../include/gsx.h"
 
+struct gsx_context;
+
 namespace gsx {
 
 // Size classes of fronts: S* are eliminated inside LDS by one workgroup, BIG by the blocked
@@ -175,5 +177,50 @@ void multilevel_nested_dissection(const std::vector<std::vector<int>>& adj, cons
                                   const std::vector<int>& verts, int leaf, NdLeafOrder leaf_order, std::vector<int>& out);
 gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order, double relax, int relax_max_f,
                              int shard_rank, int shard_world, Symbolic& S, std::string& err);
+
+// ---- Pose3 initialization (init_graph.cpp: host lowering; initialize.hip: device work) ----------------------------------
+// The pose graph of initialize::buildPoseGraph<Pose3> (gtsam/slam/InitializePose.h:36-52) over the POSE3 variables of a
+// description: node = rank of the variable among the description's POSE3 variables, the anchor (key 99999999) last.
+constexpr uint64_t kAnchorKey = 99999999;
+struct PoseGraph {
+  int n_poses = 0;                   // POSE3 variables of the description; the anchor is node n_poses
+  std::vector<int> pose_var;         // node -> variable index in the description
+  std::vector<int> node_of_var;      // variable -> node, -1: not a POSE3 variable
+  std::vector<char> touched;         // node -> some used factor holds it
+  bool all_touched = true;           // every POSE3 variable is held by a used factor
+  // edges in factor order (a prior is an edge from the anchor)
+  std::vector<int> from, to, factor;
+  std::vector<double> rot;           // 9 per edge: measured rotation, row-major
+  std::vector<double> weight;        // the rotation "precision": first entry of whiten(e0) (InitializePose3.cpp:48-51)
+  std::vector<int> adj_ptr, adj;     // node -> incident edges in factor order (createSymbolicGraph, :221-253)
+  bool anchored = true;              // every touched node is joined to the anchor by edges of non-zero weight
+};
+gsx_status build_pose_graph(const gsx_problem_desc* d, PoseGraph& G, std::string& err);
+// an owned gsx_problem_desc
+struct OwnedDesc {
+  std::vector<uint64_t> keys;
+  std::vector<int32_t> types, dims, f_type, f_rows, f_key_ptr, f_vars, f_noise_kind;
+  std::vector<int64_t> f_meas_ptr, f_noise_ptr;
+  std::vector<double> meas, noise;
+  gsx_problem_desc view() const;
+};
+// The decoupled relaxed system (InitializePose3.cpp:37-71, one of its three identical 3-dimensional parts): variables =
+// touched nodes and the anchor as VECTOR(3) in ascending key order; one 3 x 7 GSX_F_LINEAR block per edge of non-zero
+// weight (zeros here: chordal_blocks_kernel writes them), then the anchor row [I | e_1].  var_of_node: node -> variable
+// of the internal description (-1: untouched); edges: the pose-graph edges that got a block, in order.
+void lower_relaxed(const gsx_problem_desc* d, const PoseGraph& G, OwnedDesc& out, std::vector<int>& var_of_node,
+                   std::vector<int>& edges);
+// The graph of initialize::computePoses<Pose3> (InitializePose.h:57-97): the touched poses and the anchor as POSE3
+// variables, the pose-graph edges of non-zero weight as between factors with their own noise, a Unit prior on the anchor.
+void lower_anchor_graph(const gsx_problem_desc* d, const PoseGraph& G, OwnedDesc& out, std::vector<int>& var_of_node);
+
+// seams of initialize.hip into a handle (solver.hip); the pointers are device memory on the handle's device
+double* handle_jacobian_pool(gsx_context* h);   // the [A b] blocks, factor f at HostProblem::f_jac_off[f]
+double* handle_values(gsx_context* h);          // packed Values
+double* handle_delta(gsx_context* h);           // the solution of the last solve, tangent order
+void* handle_stream(gsx_context* h);            // hipStream_t
+const HostProblem& handle_problem(gsx_context* h);
+void handle_blocks_written(gsx_context* h);     // the GSX_F_LINEAR blocks were rewritten on the device: what gsx_set_block_jacobians invalidates
+void handle_values_written(gsx_context* h);     // the Values were written on the device: as after gsx_set_values
 
 }  // namespace gsx

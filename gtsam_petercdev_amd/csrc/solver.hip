@@ -3891,3 +3891,26 @@ gsx_status gsx_kernel_time(gsx_handle h, const char* name, double* avg_ms, int64
 }
 
 }  // extern "C"
+
+// ---- seams of initialize.hip (gsx_internal.h) --------------------------------------------------------------------------
+namespace gsx {
+double* handle_jacobian_pool(gsx_context* h) { return h->d_jac.p; }
+double* handle_values(gsx_context* h) { return h->d_values.p; }
+double* handle_delta(gsx_context* h) { return h->d_delta.p; }
+void* handle_stream(gsx_context* h) { return (void*)h->stream; }
+const HostProblem& handle_problem(gsx_context* h) { return h->P; }
+void handle_blocks_written(gsx_context* h) {
+  h->linearized = true;  // a linear graph IS its linearization (gsx_solve_gfg_h)
+  h->h_ready = false;
+  h->lin0_ready = false;
+  h->hdiag_ready = false;
+  h->fact_valid = false;
+  h->solved = false;
+  if (h->damp_kind != 0) h->damp_ready = false;
+}
+void handle_values_written(gsx_context* h) {
+  h->values_set = true;
+  h->values_synced = true;
+  h->linearized = h->h_ready = h->solved = false;
+}
+}  // namespace gsx

@@ -89,8 +89,20 @@ def _skew(w):
 
 
 class Rot3:
+    type_code = -1   # (a value InitializePose3 hands out; not a variable type of the backend)
+    dim = 3
+
     def __init__(self, R=None):
         self.R = np.eye(3) if R is None else np.asarray(R, dtype=float).reshape(3, 3)
+
+    def state(self):
+        return self.R.reshape(9)
+
+    @staticmethod
+    def ClosestTo(M):
+        """Rot3::ClosestTo (gtsam/geometry/SO3.cpp:202-208) on the device (gsx_closest_rotations)."""
+        from . import _lib
+        return Rot3(_lib.closest_rotations(np.asarray(M, dtype=float).reshape(1, 3, 3))[0])
 
     @staticmethod
     def Rodrigues(wx, wy=None, wz=None):
@@ -279,7 +291,8 @@ class noiseModel:
 
         @staticmethod
         def Precision(dim, precision, smart=True):
-            return noiseModel.Isotropic.Sigma(dim, 1.0 / math.sqrt(precision), smart)
+            # a zero precision is an infinite sigma, as Variance(dim, 1 / precision) gives there (NoiseModel.h:577-579)
+            return noiseModel.Isotropic.Sigma(dim, 1.0 / math.sqrt(precision) if precision != 0 else math.inf, smart)
 
     class Diagonal:
         @staticmethod
@@ -712,6 +725,101 @@ class GaussianFactorGraph(NonlinearFactorGraph):
             be.close()
         off = arrays.tangent_offsets()
         return {int(k): delta[off[i]:off[i + 1]] for i, k in enumerate(arrays.var_keys)}
+
+
+class InitializePose3:
+    """InitializePose3 (gtsam/slam/InitializePose3.h) on the device: chordal relaxation or Riemannian gradient for the
+    rotations, then one Gauss-Newton iteration for the poses (include/gsx.h: gsx_initialize_pose3 and its stages)."""
+
+    kAnchorKey = A.ANCHOR_KEY
+
+    @staticmethod
+    def buildPose3graph(graph) -> "NonlinearFactorGraph":
+        """initialize::buildPoseGraph<Pose3> (InitializePose.h:36-52): the BetweenFactor<Pose3> of the graph, and every
+        PriorFactor<Pose3> as a between factor from the anchor key with the prior's noise."""
+        out = NonlinearFactorGraph()
+        for f in graph.factors:
+            if f is None or getattr(f, "value_type", None) != A.VAR_POSE3:
+                continue
+            if f.ftype == A.F_BETWEEN:
+                out.add(f)
+            elif f.ftype == A.F_PRIOR:
+                out.add(BetweenFactor(A.ANCHOR_KEY, f.keys_[0], Pose3.from_state(f.meas), f.noise))
+        return out
+
+    @staticmethod
+    def _lower(pose3Graph, given: Optional["Values"] = None):
+        """The arrays of include/gsx.h for a graph of buildPose3graph: its keys as POSE3 variables, a between factor from
+        the anchor as the prior it came from; and `given` packed in that order (None without one)."""
+        keys = sorted({k for f in pose3Graph.factors for k in f.keys_} - {A.ANCHOR_KEY})
+        values = Values()
+        for k in keys:
+            values.insert(k, given.at(k) if given is not None else Pose3())
+        g = NonlinearFactorGraph()
+        for f in pose3Graph.factors:
+            if f.ftype != A.F_BETWEEN or getattr(f, "value_type", None) != A.VAR_POSE3:
+                raise ValueError("InitializePose3: not a graph of buildPose3graph")
+            if f.keys_[0] == A.ANCHOR_KEY:
+                g.add(PriorFactor(f.keys_[1], Pose3.from_state(f.meas), f.noise))
+            else:
+                g.add(f)
+        arr = g.to_arrays(values)
+        return arr, keys, (arr.values if given is not None else None)
+
+    @staticmethod
+    def _rotations(keys, rot) -> "Values":
+        out = Values()
+        for k, R in zip(keys, rot):
+            out.insert(k, Rot3(R))
+        return out
+
+    @staticmethod
+    def computeOrientationsChordal(pose3Graph) -> "Values":
+        from . import _lib
+        arr, keys, _ = InitializePose3._lower(pose3Graph)
+        return InitializePose3._rotations(keys, _lib.pose3_orientations_chordal(arr))
+
+    @staticmethod
+    def computeOrientationsGradient(pose3Graph, givenGuess, maxIter=10000, setRefFrame=True) -> "Values":
+        from . import _lib
+        arr, keys, given = InitializePose3._lower(pose3Graph, givenGuess)
+        return InitializePose3._rotations(keys, _lib.pose3_orientations_gradient(arr, given, maxIter, setRefFrame)[0])
+
+    @staticmethod
+    def initializeOrientations(graph) -> "Values":
+        return InitializePose3.computeOrientationsChordal(InitializePose3.buildPose3graph(graph))
+
+    @staticmethod
+    def createSymbolicGraph(pose3Graph):
+        """(adjEdgesMap: key -> factor indices in graph order, factorId2RotMap: factor index -> measured Rot3)."""
+        from . import _lib
+        arr, keys, _ = InitializePose3._lower(pose3Graph)
+        _, _, adj = _lib.pose3_init_structure(arr)
+        names = keys + [A.ANCHOR_KEY]
+        adjEdgesMap = {names[i]: lst for i, lst in enumerate(adj) if lst}
+        factorId2RotMap = {i: Pose3.from_state(f.meas).rotation() for i, f in enumerate(pose3Graph.factors)}
+        return adjEdgesMap, factorId2RotMap
+
+    @staticmethod
+    def computePoses(initialRot, posegraph, singleIter=True) -> "Values":
+        """initialize::computePoses<Pose3> (InitializePose.h:57-97).  (The reference also appends the anchor's prior to the
+        caller's posegraph; this one leaves it as it is.)"""
+        from . import _lib
+        arr, keys, _ = InitializePose3._lower(posegraph)
+        rot = np.stack([np.asarray(initialRot.at(k).matrix(), dtype=float) for k in keys]) if keys else np.zeros((0, 3, 3))
+        packed = _lib.pose3_compute_poses(arr, rot, singleIter)
+        return Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, packed)
+
+    @staticmethod
+    def initialize(graph, givenGuess=None, useGradient=False) -> "Values":
+        """InitializePose3::initialize (InitializePose3.cpp:296-319)."""
+        from . import _lib
+        arr, keys, given = InitializePose3._lower(InitializePose3.buildPose3graph(graph),
+                                                  givenGuess if (givenGuess is not None and givenGuess.size() > 0) else None)
+        p = _lib.init_pose3_params_default()
+        p.use_gradient = int(bool(useGradient))
+        packed, _ = _lib.initialize_pose3(arr, given, p)
+        return Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, packed)
 
 
 def _make_backend(arrays, backend_factory):

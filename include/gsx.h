@@ -47,6 +47,8 @@
  *                                 gtsam/nonlinear/NonlinearOptimizer.cpp:62-117,182-231)
  *   gsx_gn_optimize              GaussNewtonOptimizer::iterate
  *                                (gtsam/nonlinear/GaussNewtonOptimizer.cpp:44-66)
+ *   gsx_initialize_pose3         InitializePose3::initialize (gtsam/slam/InitializePose3.cpp:296-319) and its
+ *                                stages: see "Pose3 initialization" below
  *   gsx_solve_gfg                GaussianFactorGraph::optimize(ordering, EliminatePreferCholesky)
  *                                (gtsam/linear/GaussianFactorGraph.cpp:316-319) — the
  *                                NonlinearOptimizer::solve seam
@@ -679,6 +681,83 @@ gsx_status gsx_solve_gfg(const gsx_problem_desc* desc, const uint64_t* ordering,
  * factors, one after the other as in `meas` (blocks = NULL: solve what the handle holds).  delta_out as above. */
 gsx_status gsx_solve_gfg_h(gsx_handle h, const double* blocks, int64_t n_blocks, double* delta_out, int64_t n,
                            uint64_t* bad_key);
+
+/* ---- Pose3 initialization: InitializePose3 (gtsam/slam/InitializePose3.{h,cpp}, gtsam/slam/InitializePose.h) --------------
+ * The initial guess a Pose3 pose graph needs, in the reference's three stages: (1) chordal relaxation — one linear
+ * least-squares solve over relaxed rotation matrices, every 3 x 3 block then projected onto SO(3) (Rot3::ClosestTo);
+ * (2) optionally the Tron-Vidal Riemannian gradient iterations on the rotations; (3) Gauss-Newton on the full poses from
+ * those rotations and zero translations (one iteration by default).
+ * These calls take a description, not a handle: they build their own internal handles (direct solver, one device) and free
+ * them before returning.
+ * What is used of `desc`: GSX_F_BETWEEN on two POSE3 variables and GSX_F_PRIOR on a POSE3 variable; every other factor is
+ * ignored, as buildPoseGraph drops it (InitializePose.h:36-52).  A prior becomes a between factor from the ANCHOR (key
+ * 99999999, initialize::kAnchorKey) with the prior's noise; a variable of `desc` with that key: GSX_E_INVALID.
+ * The rotation weight of a factor is the first entry of whiten(e_0) under its noise model, which the reference takes for a
+ * precision (InitializePose3.cpp:48-51, :62): 1 (Unit), 1 / sigma (Isotropic), 1 / sigma_0 (Diagonal / Constrained; 1 when
+ * sigma_0 = 0, Constrained::whiten), R(0, 0) (Gaussian).  A robust model counts as its BASE model: a deliberate deviation —
+ * the reference's Robust::whitenInPlace also reweights (NoiseModel.h:711-712, WhitenSystem), so its precisions[0] under
+ * Huber over sigma_0 is sqrt(weight(1 / sigma_0)) / sigma_0, a value that depends on the loss's k and not on the data.
+ * A factor of weight 0 (an infinite sigma, Isotropic::Precision(6, 0)) contributes nothing to the relaxed system nor to the
+ * Gauss-Newton graph; it stays an edge of the gradient iterations, which never look at the noise.  Limit: a Diagonal /
+ * Constrained model with sigma_0 infinite and other sigmas finite is dropped from the Gauss-Newton graph as a whole as well,
+ * where the reference would keep its other five rows (gsx_create takes no infinite sigma); only Isotropic::Precision(6, 0)
+ * is a factor that truly vanishes.
+ * Rotation arrays (rot_out, rot) hold 9 doubles, row-major, per POSE3 variable of `desc`, in the order of `desc`.
+ * values_out is packed like gsx_get_values for `desc`.  The reference returns only the poses its pose graph holds; here a
+ * variable that is not POSE3, or a POSE3 variable no used factor holds, is copied from `given` by gsx_initialize_pose3
+ * (GSX_E_INVALID when there is one and given == NULL) and left as the caller filled it by gsx_pose3_compute_poses;
+ * gsx_pose3_orientations_chordal writes the identity for such a pose, gsx_pose3_orientations_gradient the rotation of
+ * `given`.
+ * GSX_E_INVALID (before any device is touched): malformed description, anchor-key collision, wrong n_out / n_rot /
+ * n_given, use_gradient without `given`.  GSX_E_NO_DEVICE: no usable device (every call but gsx_pose3_init_structure).
+ * GSX_E_INDETERMINATE: some pose is not joined to the anchor by factors of non-zero weight (no prior: the relaxed system
+ * is rank deficient and the reference throws IndeterminantLinearSystemException), or a factorization failed. */
+typedef struct gsx_init_pose3_params {
+  int32_t use_gradient;             /* 0: chordal (default) ; 1: computeOrientationsGradient            */
+  int32_t max_gradient_iterations;  /* 10000 (InitializePose3.h default)                               */
+  int32_t set_ref_frame;            /* 1                                                                */
+  int32_t single_iter;              /* 1: computePoses does one GN iteration                            */
+} gsx_init_pose3_params;
+void gsx_init_pose3_params_default(gsx_init_pose3_params* p);
+/* InitializePose3::initialize (InitializePose3.cpp:296-319); p == NULL: the defaults; gradient_iterations (may be NULL):
+ * the gradient iterations executed, 0 for chordal */
+gsx_status gsx_initialize_pose3(const gsx_problem_desc* desc, const double* given, int64_t n_given,
+                                const gsx_init_pose3_params* p, int32_t device,
+                                double* values_out, int64_t n_out, int32_t* gradient_iterations);
+/* buildPose3graph + computeOrientationsChordal (:37-114).  The relaxed 9-vector of a pose splits into the three rows of
+ * its rotation and the system into three identical ones over 3-dimensional variables that differ in the anchor prior's
+ * right-hand side (e_1, e_2, e_3) only: one internal handle of 3 x 7 GSX_F_LINEAR blocks [-w I, w Rij | 0] written on the
+ * device, one symbolic analysis, three solves, one projection kernel. */
+gsx_status gsx_pose3_orientations_chordal(const gsx_problem_desc* desc, int32_t device, double* rot_out, int64_t n_out);
+/* computeOrientationsGradient (:117-218, 256-275) from the rotations of `given` (packed Values of desc).  Two launches per
+ * iteration (gradient of every node from the old rotations, then the update by the full exponential map), no host
+ * synchronisation inside a batch of 32 iterations; stops after iteration `it` when it > 20 and the largest gradient norm
+ * is below 5e-3.  *iterations (may be NULL) = iterations executed.  The output is R^-1, or Rref R^-1 with set_ref_frame. */
+gsx_status gsx_pose3_orientations_gradient(const gsx_problem_desc* desc, const double* given, int64_t n_given,
+                                           int32_t max_iter, int32_t set_ref_frame, int32_t device,
+                                           double* rot_out, int64_t n_out, int32_t* iterations);
+/* initialize::computePoses<Pose3> (InitializePose.h:57-97): Gauss-Newton (gsx_gn_optimize; 1 iteration, or its defaults
+ * 100 / 1e-5 / 1e-5 / 0 when single_iter == 0) on the pose graph + the anchor + a Unit prior on the anchor, from
+ * (rot, zero translation); the anchor is dropped from the result. */
+gsx_status gsx_pose3_compute_poses(const gsx_problem_desc* desc, const double* rot, int64_t n_rot, int32_t single_iter,
+                                   int32_t device, double* values_out, int64_t n_out);
+/* Rot3::ClosestTo on n matrices (SO3.cpp:202-208), row-major in and out: U diag(1, 1, det(U V')) V' by one-sided Jacobi
+ * rotations in registers (no M'M is formed) and two polishing passes (csrc/init_math.h), one thread per matrix — the projection kernel of the chordal stage.  The
+ * answer is unique only when sigma_2 + sigma_3 > 0 (det > 0) or sigma_2 > sigma_3 (det < 0). */
+gsx_status gsx_closest_rotations(const double* m, int64_t n, int32_t device, double* r_out);
+/* host only, needs no device: the pose graph of buildPoseGraph<Pose3> (InitializePose.h:36-52) and the adjacency of
+ * createSymbolicGraph (InitializePose3.cpp:221-253).  Nodes: the POSE3 variables of desc in its order (0 .. P-1), the anchor
+ * = P.  Edges in factor order, a prior as an edge from the anchor: edge_from / edge_to [*n_edges] (call once with NULL
+ * arrays for *n_edges); adj_ptr [P + 2], adj [2 * n_edges] = the edges at each node in factor order; adj_cap = the
+ * capacity of adj (GSX_E_INVALID when too small).  Any array may be NULL. */
+gsx_status gsx_pose3_init_structure(const gsx_problem_desc* desc, int32_t* n_edges, int32_t* edge_from, int32_t* edge_to,
+                                    int32_t* adj_ptr, int32_t* adj, int64_t adj_cap);
+/* Stage times (ms) of the LAST initializer call of the process (not thread-safe; for tools/init_probe.py), n = 8:
+ * [0] host: lowering + ordering + symbolic analysis + upload of the relaxed system; [1] chordal_blocks_kernel; [2] the three
+ * relaxed solves; [3] closest_rotation_kernel; [4] host: the same for the anchor graph; [5] pose_states_kernel +
+ * gsx_gn_optimize; [6] the gradient iterations; [7] the number of gradient iterations executed.  [1]-[3], [5], [6] are HIP
+ * events on the internal handle's stream; a stage that did not run is 0. */
+gsx_status gsx_pose3_init_timings(double* out_ms, int32_t n);
 
 /* ---- dense kernel exposed for unit parity (gtsam/base/cholesky.cpp:108-159) -- */
 /* In-place partial Cholesky of an n x n column-major symmetric matrix (upper

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Where the time of gsx_initialize_pose3 goes, beside the LM iteration of the same graph on the same build.
+
+    python tools/init_probe.py [--poses 100000] [--reps 5] [--warmup 2] [--gradient-iterations 100] [--out FILE.json]
+
+Runs the chordal initializer, and the gradient one with a fixed number of iterations, on the synthetic pose3 graph of
+bench.py (datasets.synth_manhattan_pose3, seed 42; the reader-style prior is on its first pose) and prints one JSON line:
+per stage the median over the repetitions of the times the library keeps for its last call (gsx_pose3_init_timings: HIP
+events on the internal handle's stream for the device stages, a host clock for the two analyses), the wall time of the
+whole call (a host clock around a call that ends synchronised), and ms per LM trial of the same graph measured as bench.py
+measures it.  Every shape is warmed up first; a tracing profiler must not be attached (end-to-end numbers).
+Without a GPU the tool only builds the graph and its structure (--host-only does the same where there is one)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from gtsam_petercdev_amd import _abi as A, _lib, datasets  # noqa: E402
+
+
+def timed_runs(call, reps, warmup):
+    for _ in range(warmup):
+        call()
+    wall, stages = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        call()
+        wall.append(1e3 * (time.perf_counter() - t0))
+        stages.append(_lib.pose3_init_timings())
+    out = {k: statistics.median(s[k] for s in stages) for k in stages[0]}
+    out["whole_call_wall_ms"] = statistics.median(wall)
+    out["whole_call_wall_ms_min_max"] = [min(wall), max(wall)]
+    return out
+
+
+def lm_ms_per_trial(arr, steps, warmup, lam=1e-5):
+    be = _lib.product_backend(arr)
+    be.set_ordering(be.compute_ordering(A.ORDER_ND))
+    be.set_profiling(-1)
+    for _ in range(warmup):
+        be.lm_trial(True, lam, False)
+    be.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        be.lm_trial(True, lam, False)
+    be.synchronize()
+    ms = 1e3 * (time.perf_counter() - t0) / steps
+    be.close()
+    return ms
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--poses", type=int, default=100000)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--gradient-iterations", type=int, default=100)
+    ap.add_argument("--lm-steps", type=int, default=20)
+    ap.add_argument("--host-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    arr = datasets.synth_manhattan_pose3(args.poses, seed=42)
+    t0 = time.perf_counter()
+    ef, _, adj = _lib.pose3_init_structure(arr)
+    out = {"workload": f"pose3_{args.poses}", "n_poses": arr.n_vars, "n_factors": arr.n_factors, "n_edges": int(ef.size),
+           "max_node_degree": max(len(a) for a in adj), "structure_host_ms": 1e3 * (time.perf_counter() - t0)}
+    if args.host_only or _lib.device_count() == 0:
+        out["device"] = None
+        print(json.dumps(out))
+        return out
+    out["chordal"] = timed_runs(lambda: _lib.initialize_pose3(arr), args.reps, args.warmup)
+    p = _lib.init_pose3_params_default()
+    p.use_gradient, p.max_gradient_iterations = 1, args.gradient_iterations
+    g = timed_runs(lambda: _lib.initialize_pose3(arr, arr.values, p), args.reps, args.warmup)
+    g["ms_per_gradient_iteration"] = g["gradient_ms"] / max(g["gradient_iterations"], 1.0)
+    out["gradient"] = g
+    out["lm_ms_per_trial"] = lm_ms_per_trial(arr, args.lm_steps, 3)
+    init, _ = _lib.initialize_pose3(arr)
+    be = _lib.product_backend(arr)
+    out["error_of_the_graphs_own_values"] = be.error()
+    be.set_values(init)
+    out["error_after_chordal_initialization"] = be.error()
+    be.close()
+    assert np.all(np.isfinite(init))
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return out
+
+
+if __name__ == "__main__":
+    main()
