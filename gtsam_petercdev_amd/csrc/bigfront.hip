@@ -1412,7 +1412,10 @@ __global__ void __launch_bounds__(256) backsolve_tree_kernel(DevSymbolic S, Back
       if (low && F <= kBsSmallF) backsolve_small_body<true>(S, f, arena, delta, status, pool);
       else if (low && F <= 2 * kBsSmallF) backsolve_small2_body<true>(S, f, arena, delta, status, pool);
       else backsolve_panels_body<true>(S, f, arena, delta, status, pool);
-      __syncthreads();  // every store of the solution has drained (s_waitcnt vmcnt(0) before the barrier)
+      // every wave waits for its own agent-scope stores of the solution before the barrier (the barrier alone does not:
+      // the compiler puts no vmcnt wait in front of s_barrier); behind it the children may be published
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
       // the first tree child (the deepest subtree: the host sorted them) is solved by this workgroup right away, the
       // others are published: one claim of a range of entries, then one entry per lane
       const int c0 = Q.child_ptr[f], nc = Q.child_ptr[f + 1] - c0;

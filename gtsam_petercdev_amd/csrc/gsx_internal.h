@@ -15,6 +15,7 @@ namespace gsx {
 constexpr int kSmallMaxN = 140;     // 140^2 * 8 B = 156.8 KB <= 160 KB LDS
 constexpr int kTile = 32;           // tile edge of the blocked big-front path
 constexpr int kGatherChunk = 64;    // sources per gather segment: one wave, one source record per lane
+constexpr int kMaxTreeTiers = 8;    // tiers of the tree kernels, the medium tier included (one start-list cursor each)
 constexpr int kLeafMaxF = 16;      // leaf cliques with at most this many frontal scalars use the panel-only kernel
 constexpr int kLeafMaxPanel = 8192; // doubles of LDS (n x F) a lean leaf may use: 64 KB
 // MEDIUM fronts: more rows than fit LDS as a square, but whose n x F frontal panel does.  One workgroup eliminates such a

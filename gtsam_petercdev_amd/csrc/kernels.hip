@@ -1913,13 +1913,22 @@ struct FrontScratch {
 
 // A launch that asks for more LDS than a CU has must never reach the GPU (the hardware faults instead of refusing):
 // dynamic + the kernel's static LDS against the 160 KB of a gfx950 CU.  A refused launch leaves its fronts unfactored,
-// which the status words / the parity tests show; the symbolic analysis sizes every class so that this never fires.
-static bool lds_fits(const void* kernel, size_t dynamic_bytes, const char* what) {
+// so it FAILS the factorization: the status words are raised as if the launch's first front had failed (the solve then
+// returns an error instead of a finite step from a stale arena).  The symbolic analysis sizes every class so that this
+// never fires.
+__global__ void refused_launch_kernel(DevStatus* status, const int* fronts) {
+  atomicAdd(&status->n_fail, 1);
+  atomicMin(&status->first_front, fronts[0]);
+}
+static bool lds_fits(const void* kernel, size_t dynamic_bytes, const char* what, DevStatus* status, const int* fronts,
+                     hipStream_t st) {
   hipFuncAttributes a;
   size_t fixed = 8192;
   if (hipFuncGetAttributes(&a, kernel) == hipSuccess) fixed = a.sharedSizeBytes;
   if (dynamic_bytes + fixed <= (size_t)160 * 1024) return true;
-  fprintf(stderr, "gsx: %s needs %zu + %zu bytes of LDS: launch refused\n", what, dynamic_bytes, fixed);
+  fprintf(stderr, "gsx: %s needs %zu + %zu bytes of LDS: launch refused, the factorization fails\n", what, dynamic_bytes,
+          fixed);
+  refused_launch_kernel<<<1, 1, 0, st>>>(status, fronts);
   return false;
 }
 
@@ -2556,7 +2565,7 @@ __device__ __forceinline__ void front_medium_body(const DevProblem& P, const Dev
     }
   }
   FS_ADD(1)
-  // children, in child order (a barrier — which also drains the arena stores — between one child and the next)
+  // children, in child order (a barrier, which orders the workgroup's own arena accesses, between one child and the next)
   auto child = [&](int k) -> ChildRec { return k < kChildStage ? mcrec[k] : S.child_recs[fr.child_ptr + k]; };
   if (nchild > 0) {
     const ChildRec c0 = child(0);
@@ -2670,7 +2679,7 @@ void launch_front_medium(const DevProblem& P, const DevSymbolic& S, const int* i
     hipFuncSetAttribute((const void*)front_medium_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
     attr = true;
   }
-  if (count && lds_fits((const void*)front_medium_kernel, ((size_t)max_panel + max_n) * sizeof(double), "front_medium"))
+  if (count && lds_fits((const void*)front_medium_kernel, ((size_t)max_panel + max_n) * sizeof(double), "front_medium", status, ids, st))
     front_medium_kernel<<<count, 512, ((size_t)max_panel + max_n) * sizeof(double), st>>>(P, S, ids, H, damp, scalars, arena,
                                                                                           status);
 }
@@ -2681,7 +2690,7 @@ void launch_front_medium(const DevProblem& P, const DevSymbolic& S, const int* i
 // and then climbs: it tells the parent that one more child has arrived (one device-scope atomic), and when it was the
 // LAST to arrive it eliminates the parent itself — whose children's Schur complements are then all in the arena, written
 // by this or by other workgroups: the Schur complements travel with agent-scope stores and loads (past the per-XCD L2s),
-// ordered by the workgroup's own wait for its stores before the atomic — a release / acquire fence pair instead writes
+// ordered by every wave's own wait for its stores (s_waitcnt vmcnt(0)) before the barrier in front of the atomic — a release / acquire fence pair instead writes
 // back and invalidates a whole L2 per front, measured at 5x the level-by-level time.  Nobody ever waits: a
 // workgroup that is not the last arrival claims the next start front, and leaves when there is none.  The extend-add
 // stays a pull in child order, so the numbers do not depend on who arrives when (bitwise reproducible).
@@ -2706,7 +2715,12 @@ __global__ void __launch_bounds__(512, 4) front_tree_kernel(DevProblem P, DevSym
 #ifdef GSX_STAMP
       unsigned long long hs0 = wall_clock64();
 #endif
-      __syncthreads();  // (drains every store of the workgroup: s_waitcnt vmcnt(0) before the barrier)
+      // The hand-off: EVERY wave waits for its own agent-scope stores of this front (the Schur complement) before the
+      // barrier; behind the barrier all of the workgroup's stores have therefore completed, and only then does thread 0
+      // count the front in at its parent.  (The barrier alone does not do it: the compiler puts no vmcnt wait in front
+      // of s_barrier, a wave may reach it with stores in flight.)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
       if (threadIdx.x == 0) {
         int nxt = -1;
         const int p = T.up[f];
@@ -2758,7 +2772,8 @@ __global__ void __launch_bounds__(512) front_tree_med_kernel(DevProblem P, DevSy
     while (f >= 0) {
       if (S.front_recs[f].n > kSmallMaxN) front_medium_body<true>(P, S, f, H, damp, lambda, arena, status, L, sc);
       else front_small_body<true>(P, S, f, H, damp, lambda, arena, status, L, sc);
-      __syncthreads();  // (drains every store of the workgroup)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave: its stores of this front are complete (see front_tree_kernel)
+      __syncthreads();
       if (threadIdx.x == 0) {
         int nxt = -1;
         const int p = T.up[f];
@@ -2781,7 +2796,7 @@ void launch_front_tree_med(const DevProblem& P, const DevSymbolic& S, const Tree
     hipFuncSetAttribute((const void*)front_tree_med_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
     attr = true;
   }
-  if (T.nstart <= 0 || !lds_fits((const void*)front_tree_med_kernel, lds_bytes, "front_tree_med")) return;
+  if (T.nstart <= 0 || !lds_fits((const void*)front_tree_med_kernel, lds_bytes, "front_tree_med", status, T.start, st)) return;
 #ifdef GSX_STAMP
   fs_stamp_zero();
 #endif
@@ -2800,7 +2815,7 @@ void launch_front_tree(const DevProblem& P, const DevSymbolic& S, const TreeArgs
   }
   if (T.nstart <= 0) return;
   const size_t lds = ((size_t)max_n * max_n + max_n) * sizeof(double);
-  if (!lds_fits((const void*)front_tree_kernel, lds, "front_tree")) return;
+  if (!lds_fits((const void*)front_tree_kernel, lds, "front_tree", status, T.start, st)) return;
   // as many workgroups as can be resident (LDS, 2048 threads a CU); the rest would only find the start list empty
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>({(size_t)(156 * 1024) / (lds + 2048), (size_t)2048 / threads, 16}));
   const int grid = std::min(T.nstart, 256 * per_cu);
@@ -2824,7 +2839,8 @@ void launch_front_small(const DevProblem& P, const DevSymbolic& S, const int* id
 #ifdef GSX_STAMP
   fs_stamp_zero();
 #endif
-  if (count && lds_fits((const void*)front_small_kernel, ((size_t)max_n * max_n + max_n) * sizeof(double), "front_small"))
+  if (count && lds_fits((const void*)front_small_kernel, ((size_t)max_n * max_n + max_n) * sizeof(double), "front_small", status, ids,
+                        st))
     front_small_kernel<<<count, threads, ((size_t)max_n * max_n + max_n) * sizeof(double), st>>>(P, S, ids, H, damp, scalars,
                                                                                          arena, status);
 #ifdef GSX_STAMP

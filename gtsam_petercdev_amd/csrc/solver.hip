@@ -997,7 +997,12 @@ gsx_status upload_symbolic(gsx_context* c) {
   {
     c->tree_tiers.clear();
     const int nb = (int)S.tree_bounds.size();
-    const int ntier = std::min<int>((int)S.tree_start_ptr.size() - 1, kTreeCursors);
+    static_assert(kMaxTreeTiers <= kTreeCursors, "a start-list cursor per tier");
+    const int ntier = (int)S.tree_start_ptr.size() - 1;   // (symbolic.cpp keeps at most kMaxTreeTiers)
+    if (ntier > kTreeCursors) {
+      c->err = "more tree tiers than start-list cursors";
+      return GSX_E_STATE;
+    }
     for (int t = 0; t < ntier; ++t) {
       int maxn = 0;
       size_t lds = 0;   // the medium tier: doubles of LDS of its most demanding front

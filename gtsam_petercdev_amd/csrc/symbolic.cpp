@@ -689,6 +689,12 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
       S.tree_bounds = {67, kSmallMaxN};
       S.tree_threads = {256, 512};
     }
+    // one start-list cursor per tier, the medium tier included: the bounds past kMaxTreeTiers - 1 are dropped, and fronts
+    // taller than the last bound kept are no tree fronts — they go to the upper schedule (below)
+    if ((int)S.tree_bounds.size() > kMaxTreeTiers - 1) {
+      S.tree_bounds.resize(kMaxTreeTiers - 1);
+      S.tree_threads.resize(kMaxTreeTiers - 1);
+    }
     S.tree_tier.assign(nfr, -1);
     S.tree_up.assign(nfr, -1);
     S.tree_npend.assign(nfr, 0);

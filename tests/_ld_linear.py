@@ -21,6 +21,9 @@ mpmath (test_host_linear_judge.py) covers n <= 40 at small kappa_2 only.
 The bounds are backward-error bounds: they do not depend on the conditioning of the problem (4 carries kappa_2
 explicitly) nor on the rounding of a second implementation.  gamma = k u, u = 2^-53; k_factor / k_solve below derive k.
 
+VectorJudge (below) takes measures (2) and (3) with the same bounds and k without ever forming an n x n array, for systems
+of several thousand scalars.
+
 Everything is kept in VARIABLE coordinates (scalar i of variable v at tangent_offsets[v] + i, the layout of solve()'s
 result); gather() also returns the elimination order of the scalars, in which R is upper triangular.
 """
@@ -337,3 +340,90 @@ class Judge:
         r = covariance_ratio(block, S[np.ix_(idx, idx)], smax, kappa)
         assert r <= self.ks, (what, "covariance", keys, r, self.ks)
         return r
+
+
+# ---- the same measures (2) and (3) without an n x n array: for systems too large for the dense judge -------------------------
+def gather_cliques(backend, off, n):
+    """[(frontal scalars, column scalars, [R S] in longdouble, d in longdouble)] per clique, variable coordinates.  Rows
+    of different cliques share no product, so R'v and |R|'|R||x| are sums over this list (the order does not matter)."""
+    parent, fronts = backend.get_tree()
+    seen = np.zeros(n, bool)
+    out = []
+    for c, (fv, sv) in enumerate(fronts):
+        fi = np.concatenate([np.arange(off[v], off[v + 1]) for v in fv])
+        si = np.concatenate([np.arange(off[v], off[v + 1]) for v in sv]) if len(sv) else np.zeros(0, np.int64)
+        RSd = np.asarray(backend.conditional(c), dtype=np.float64)
+        assert RSd.shape == (fi.size, fi.size + si.size + 1), (c, RSd.shape, fi.size, si.size)
+        assert not seen[fi].any(), "a variable is frontal in two cliques"
+        seen[fi] = True
+        assert np.all(np.tril(RSd[:, :fi.size], -1) == 0), ("clique", c, "R is not upper triangular")
+        out.append((fi, np.concatenate([fi, si]), RSd[:, :-1].astype(LD), RSd[:, -1].astype(LD)))
+    assert seen.all(), "a variable is frontal in no clique"
+    return out
+
+
+class VectorJudge:
+    """Measures (2) and (3) with the bounds and the k of Judge, every product a vector: R'd and |R'||d| summed clique by
+    clique, Hd x, |A'||A||x|, g, |A'||b| and the diagonal of A'A (the damping) summed factor by factor, in longdouble."""
+
+    def __init__(self, arrays, jac):
+        self.arrays = arrays
+        self.off = np.asarray(arrays.tangent_offsets(), dtype=np.int64)
+        self.n = n = int(self.off[-1])
+        joff = arrays.jacobian_offsets()
+        self.blocks = []
+        self.g = np.zeros(n, LD)
+        self.absg = np.zeros(n, LD)
+        self.diagH = np.zeros(n, LD)
+        rows = np.zeros(n, np.int64)
+        for f in range(arrays.n_factors):
+            vs = arrays.f_vars[arrays.f_key_ptr[f]:arrays.f_key_ptr[f + 1]]
+            m = int(arrays.f_rows[f])
+            if m == 0 or len(vs) == 0:
+                continue
+            idx = np.concatenate([np.arange(self.off[v], self.off[v + 1]) for v in vs])
+            assert len(set(idx.tolist())) == idx.size, "a factor names a variable twice"
+            Ab = np.asarray(jac[joff[f]:joff[f + 1]], dtype=np.float64).reshape(idx.size + 1, m).T.astype(LD)
+            A, b = Ab[:, :-1], Ab[:, -1]
+            self.blocks.append((idx, A, b))
+            self.g[idx] += np.dot(A.T, b)
+            self.absg[idx] += np.dot(np.abs(A).T, np.abs(b))
+            self.diagH[idx] += np.sum(A * A, axis=0)
+            rows[idx] += m
+        self.m = int(rows.max()) + 1          # + 1: the damping row of that scalar (as LinearSystem.m)
+        self.kf = k_factor(self.m, self.n)
+        self.ks = k_solve(self.m, self.n)
+
+    def damping(self, lam, diag, min_diagonal=1e-6, max_diagonal=1e32):
+        if not lam > 0:
+            return np.zeros(self.n, LD)
+        d = np.clip(self.diagH, LD(min_diagonal), LD(max_diagonal)) if diag else np.ones(self.n, LD)
+        return LD(lam) * d
+
+    def backward(self, backend, x, lam, diag):
+        """(rhs, solve) ratios in u."""
+        n = self.n
+        cliques = gather_cliques(backend, self.off, n)
+        x = np.asarray(x, LD)
+        ax = np.abs(x)
+        Rtd, aRtad, aRtaRx = np.zeros(n, LD), np.zeros(n, LD), np.zeros(n, LD)
+        for fi, cols, W, d in cliques:
+            aW = np.abs(W)
+            Rtd[cols] += np.dot(W.T, d)
+            aRtad[cols] += np.dot(aW.T, np.abs(d))
+            aRtaRx[cols] += np.dot(aW.T, np.dot(aW, ax[cols]))
+        damp = self.damping(lam, diag)
+        Hx, aHax = damp * x, damp * ax
+        for idx, A, _ in self.blocks:
+            aA = np.abs(A)
+            Hx[idx] += np.dot(A.T, np.dot(A, x[idx]))
+            aHax[idx] += np.dot(aA.T, np.dot(aA, ax[idx]))
+        return _ratio(Rtd - self.g, aRtad + self.absg), _ratio(Hx - self.g, aRtaRx + aHax + self.absg)
+
+    def check_backward(self, backend, x, lam, diag, what):
+        r, s = self.backward(backend, x, lam, diag)
+        print(f"{what} lam={lam:g} diag={int(diag)} n={self.n} m={self.m}: rhs {r:.2f}u (k {self.kf}), "
+              f"solve {s:.2f}u (k {self.ks})")
+        assert r <= self.kf, (what, "rhs", lam, diag, r, self.kf)
+        assert s <= self.ks, (what, "solve", lam, diag, s, self.ks)
+        return r, s

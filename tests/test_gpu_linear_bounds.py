@@ -6,12 +6,23 @@ and of the oracle's rounding.  The cases are the smallest shapes that reach each
 medium, blocked, tree), each back-substitution kernel and each (child class, parent class) pair of marginals.hip; the
 last test asserts that every front class really occurred.
 
+The dependency-driven launches (front_tree, front_tree_med, backsolve_tree: one workgroup's results consumed by another
+inside the launch) are also judged on deep and wide trees (test_deep_trees, test_wide_trees; _linear_cases.DEEP_DENSE /
+DEEP_WIDE): chains 597 and 1397 fronts high that one workgroup climbs alone, parents with 65 / 66 / 130 tree children,
+a caterpillar, chains in the second and in the medium tier, a pose graph under the reference's COLAMD ordering, and
+forests with more tickets / start fronts than the launches' grids — each with the tree kernels on and off, over the
+neighbouring-lambda sequence on one handle, with bit-equal repeats.  These judge the result of one run each: they cannot
+show a race in the hand-off and do not loop to look for one.
+
 gsx_get_conditional reports the factorization the arena holds: after solve(lambda, diag) the DAMPED one of that call
 (solver.hip: fact_lambda), after a marginal query the undamped one.  Measures (1) and (2) are therefore taken right after
 each solve, against Hd of that lambda; measure (3) does not depend on it.
 
 Every test prints its ratios in units of u (or of u kappa_2); the worst of the module are printed by the last test.
 Measured on the MI355X: factor 29.1 u, rhs 18.6 u, solve 6.6 u, step 2.1 u kappa_2, marginals 1.1 u kappa_2.
+The deep trees (both schedules alike): factor 4.9 u, rhs 2.9 u, solve 1.8 u, step 0.25 u kappa_2 against k of 1100 to 3600
+(factor, rhs) and 3100 to 10900 (solve, step); the wide trees: rhs 2.2 u, solve 1.8 u against k of 7800 to 12600 and 23400
+to 37800; nine tiers: factor 13.7 u, rhs 7.1 u, solve 2.6 u.
 """
 import numpy as np
 import pytest
@@ -121,6 +132,96 @@ def test_tree_kernels(gpu, name, mode, monkeypatch):
                 for (f, s), c in zip(fronts, gb.front_classes()) if c & 4]
         assert min(rows) <= 67 < max(rows), (min(rows), max(rows))
     _judge(gb, judge, f"tree kernels {name} {mode} classes {sorted(cls)}", step=False)
+
+
+# ---- the dependency-driven launches on deep and wide trees ------------------------------------------------------------------------
+_DEEP_JUDGES = {}          # case -> (jacobians, Judge): the system and its refined x* are shared by the two schedules of a case
+
+
+def _deep_case(gpu, name, mode, monkeypatch, table):
+    """The case's shape asserted host-only (tree kernels on), then the device handle under the schedule of `mode`."""
+    maker, env, amalgamation = table[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    arr, ordering = maker()
+    cases.assert_deep_shape(name, cases.tree_shape(arr, ordering, amalgamation))
+    if mode == "levels":
+        monkeypatch.setenv("GSX_TREE_TIERS", "0")
+    gb = gpu.product_backend(arr)
+    gb.set_amalgamation(*amalgamation)
+    gb.set_ordering(ordering)
+    cls = set(int(c) for c in gb.front_classes())
+    SEEN.update(cls)
+    st = gb.stats()
+    assert st["n_big_fronts"] == 0 and (st["n_tree_fronts"] > 0) == (mode == "tree")
+    assert any(c & 4 for c in cls) == (mode == "tree"), cls
+    gb.linearize()
+    return arr, gb, cls
+
+
+def _repeat_is_bit_equal(gb, lam, diag, what):
+    x = gb.solve(lam, diag)
+    assert np.array_equal(x, gb.solve(lam, diag)), (what, "two solves at one lambda differ")
+
+
+@pytest.mark.parametrize("mode", ["tree", "levels"])
+@pytest.mark.parametrize("name", list(cases.DEEP_DENSE))
+def test_deep_trees(gpu, name, mode, monkeypatch):
+    """A workgroup that climbs (and descends) hundreds of fronts alone; parents with 65 / 66 / 130 tree children (the
+    publish loop's one, two and three trips of 64 lanes; a pending counter counted down by as many workgroups); a chain in
+    the second tier, one in the medium tier, and a pose graph under the reference's COLAMD ordering.  One handle, the
+    neighbouring-lambda sequence: a counter not restored, a cursor not zeroed or a ticket of the previous epoch shows in
+    the next solve, which is judged for ITS lambda.  Each schedule is judged on its own against the system."""
+    arr, gb, cls = _deep_case(gpu, name, mode, monkeypatch, cases.DEEP_DENSE)
+    jac = gb.jacobians()
+    kept = _DEEP_JUDGES.pop(name, None)     # (the second schedule takes the judge out again: nothing stays behind)
+    if kept is None:
+        kept = _DEEP_JUDGES[name] = (jac, J.Judge(arr, jac))
+    assert np.array_equal(jac, kept[0])
+    what = f"deep {name} {mode} classes {sorted(cls)}"
+    _repeat_is_bit_equal(gb, *cases.DEEP_LAMBDAS[0], what)
+    _judge(gb, kept[1], what, lambdas=cases.DEEP_LAMBDAS, step=name != "colamd_pose2")
+
+
+_WIDE_STEPS = {}           # case -> {(lambda, diag): the step of the first schedule that ran}
+
+
+@pytest.mark.parametrize("mode", ["tree", "levels"])
+@pytest.mark.parametrize("name", list(cases.DEEP_WIDE))
+def test_wide_trees(gpu, name, mode, monkeypatch):
+    """More tickets than backsolve_tree's grid (1300 roots), more start fronts than front_tree's (2100), and a chain 1397
+    fronts high: measures (2) and (3) from the vector judge, bit-equal repeats, and the two schedules against each other
+    at the tolerance of test_tree_kernels_against_the_level_launches."""
+    arr, gb, cls = _deep_case(gpu, name, mode, monkeypatch, cases.DEEP_WIDE)
+    judge = J.VectorJudge(arr, gb.jacobians())
+    what = f"wide {name} {mode} classes {sorted(cls)}"
+    _repeat_is_bit_equal(gb, *cases.DEEP_LAMBDAS[0], what)
+    steps = {}
+    for k, (lam, diag) in enumerate(cases.DEEP_LAMBDAS):
+        x = gb.solve(lam, diag)
+        r, s = judge.check_backward(gb, x, lam, diag, what)
+        WORST["rhs"], WORST["solve"] = max(WORST["rhs"], r), max(WORST["solve"], s)
+        if (lam, diag) in steps:
+            assert np.array_equal(x, steps[(lam, diag)]), (what, "the same lambda later on the handle", lam)
+        steps[(lam, diag)] = x
+    other = _WIDE_STEPS.setdefault(name, steps)
+    for key, x in steps.items():
+        np.testing.assert_allclose(x, other[key], rtol=1e-9, atol=1e-11 * np.abs(other[key]).max(), err_msg=f"{what} {key}")
+
+
+def test_nine_tiers_are_clamped(gpu, monkeypatch):
+    """A GSX_TREE_TIERS list longer than the start-list cursors: the extra tiers' fronts go to the upper schedule (none is
+    left unfactored), and the result holds the backward-error bounds."""
+    monkeypatch.setenv("GSX_TREE_TIERS", "40:128,50:128,60:256,67:256,75:256,85:512,95:512,105:512,140:512")
+    gb, judge, cls = _device_case(gpu, cases.tree_arrays("pose3"), A.ORDER_ND, cases.TREE_AMALGAMATION)
+    rows = [sum(int(judge.sys.arrays.var_dims[v]) for v in f + s) + 1 for f, s in gb.get_tree()[1]]
+    tree_rows = [r for r, c in zip(rows, gb.front_classes()) if c & 4]
+    # seven bounds are kept (the eighth cursor is the medium tier's): tree fronts stop at 95 rows, and the 115-row LDS
+    # front, which the ninth tier would have held, is eliminated by its level's launch
+    upper = [r for r, c in zip(rows, gb.front_classes()) if c == 1]
+    assert tree_rows and upper and max(tree_rows) <= 95 < max(upper) and min(tree_rows) <= 40, (tree_rows, upper)
+    assert gb.stats()["n_big_fronts"] == 0
+    _judge(gb, judge, f"nine tiers classes {sorted(cls)}", step=False)
 
 
 # ---- structure ----------------------------------------------------------------------------------------------------------------

@@ -1,10 +1,14 @@
 """Pins the extended-precision judge of tests/_ld_linear.py without a GPU: its longdouble arithmetic against mpmath at 50
 digits, the CPU oracle under its four measures on every linear case the device is judged on, and four mutations of a
 correct oracle result that must each fail the measure that owns them (the judge can bite without touching a kernel).
+The deep and wide trees of the dependency-driven launches (chains, brooms, a caterpillar, forests, a pose graph under
+COLAMD) have their shapes asserted here host-only, and the oracle is judged on them: densely, or by the vector judge, which
+is pinned against the dense one.
 
 Measured (CPU oracle, worst over the cases): factor 13.5 u, rhs 8.3 u, solve 5.2 u against k of 100 to 3700 (factor, rhs)
 and 190 to 11000 (solve); step 1.6 and marginals 1.1 u kappa_2 against the same k, kappa_2 between 5 and 1000 (2e10 for
-the marginals of the bundle-adjustment case, whose gauge only weak priors hold)."""
+the marginals of the bundle-adjustment case, whose gauge only weak priors hold).  On the deep and wide trees: factor 4.6 u,
+rhs 2.8 u, solve 1.9 u, step 0.27 u kappa_2 (k of 1100 to 12600 and 3100 to 37800)."""
 import mpmath
 import numpy as np
 import pytest
@@ -135,6 +139,44 @@ def test_oracle_nonlinear_cases(oracle, name):
         print(f"oracle {name}: marginals {worst:.3f} u*kappa (kappa {judge.sigma()[1]:.1f}, k {judge.ks})")
 
 
+# ---- the deep and wide trees of the dependency-driven launches ---------------------------------------------------------------
+@pytest.mark.parametrize("name", list(cases.DEEP_DENSE) + list(cases.DEEP_WIDE))
+def test_deep_and_wide_shapes(name, monkeypatch):
+    """What each case is aimed at (depth, children of one parent, tickets, start fronts, tier) is a fact of the symbolic
+    analysis: asserted here without a GPU, and again by the device tests before they judge."""
+    maker, env, amalgamation = {**cases.DEEP_DENSE, **cases.DEEP_WIDE}[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    arr, ordering = maker()
+    shape = cases.tree_shape(arr, ordering, amalgamation)
+    print(name, {k: v for k, v in shape.items() if k != "tree_rows"}, "rows", min(shape["tree_rows"]), max(shape["tree_rows"]))
+    cases.assert_deep_shape(name, shape)
+    monkeypatch.setenv("GSX_TREE_TIERS", "0")
+    off = cases.tree_shape(arr, ordering, amalgamation)
+    assert off["tree_fronts"] == 0 and not any(c & 4 for c in off["classes"]) and off["n_big_fronts"] == 0, off
+
+
+@pytest.mark.parametrize("name", list(cases.DEEP_DENSE))
+def test_oracle_deep_dense_cases(oracle, name):
+    """The oracle under the unchanged k on every densely judged deep case (m, the longest accumulation, is 267 on the hub of
+    the 130-arm broom).  Measure (4) where kappa_2 allows it: the pose graph under COLAMD has kappa_2 of 1e6."""
+    arr, ordering = cases.DEEP_DENSE[name][0]()
+    ob, judge = _oracle_case(oracle, arr, ordering)
+    _judge_oracle(ob, judge, f"oracle {name}", lambdas=cases.DEEP_LAMBDAS, step=name != "colamd_pose2")
+
+
+@pytest.mark.parametrize("name", list(cases.DEEP_WIDE))
+def test_oracle_wide_cases(oracle, name):
+    """Measures (2) and (3) of the oracle on the cases too large for the dense judge."""
+    arr, ordering = cases.DEEP_WIDE[name][0]()
+    ob = oracle.oracle_backend(arr)
+    ob.set_ordering(ordering)
+    ob.linearize()
+    judge = J.VectorJudge(arr, ob.jacobians())
+    for lam, diag in cases.DEEP_LAMBDAS:
+        judge.check_backward(ob, ob.solve(lam, diag), lam, diag, f"oracle {name}")
+
+
 # ---- mutations of a correct result: each must fail the measure that owns it ----------------------------------------------------
 class _Frozen:
     """A backend's tree and conditionals, copied: what gather() reads, open to mutation."""
@@ -219,3 +261,46 @@ def test_mutation_one_structural_zero_set_to_1e_minus_30(correct):
         frozen.conds[c] = keep
     print(f"structural zero = 1e-30: factor {f:.3g}u rhs {r:.3g}u solve {s:.3g}u")
     assert f == float("inf")
+
+
+# ---- the vector judge ---------------------------------------------------------------------------------------------------------------
+def test_vector_judge_agrees_with_the_dense_judge(correct):
+    """Measures (2) and (3) summed clique by clique and factor by factor against the same two from the n x n arrays."""
+    judge, frozen, _, x, lam = correct
+    vj = J.VectorJudge(judge.sys.arrays, _jac_of(judge))
+    assert (vj.m, vj.n, vj.kf, vj.ks) == (judge.sys.m, judge.sys.n, judge.kf, judge.ks)
+    for lm, diag in [(lam, True), (0.0, False), (1e-3, False)]:
+        _, r, s = judge.backward(frozen, x, lm, diag)
+        rv, sv = vj.backward(frozen, x, lm, diag)
+        print(f"lam {lm:g}: dense rhs {r:.6f}u solve {s:.6f}u, vector rhs {rv:.6f}u solve {sv:.6f}u")
+        assert abs(rv - r) <= 1e-6 * r and abs(sv - s) <= 1e-6 * s
+
+
+def _jac_of(judge):
+    """The packed [A b] a judge was built from, back from its factor blocks (column-major per factor, b last)."""
+    arr = judge.sys.arrays
+    joff = arr.jacobian_offsets()
+    jac = np.zeros(int(joff[-1]))
+    blocks = iter(judge.sys.blocks)
+    for f in range(arr.n_factors):
+        if int(arr.f_rows[f]) == 0 or arr.f_key_ptr[f + 1] == arr.f_key_ptr[f]:
+            continue
+        _, Af, bf = next(blocks)
+        jac[joff[f]:joff[f + 1]] = np.column_stack([Af, bf]).astype(np.float64).T.ravel()
+    return jac
+
+
+def test_vector_mutation_one_d_entry_by_1e_minus_10(correct):
+    judge, frozen, _, x, lam = correct
+    vj = J.VectorJudge(judge.sys.arrays, _jac_of(judge))
+    c = _child(frozen)
+    keep = frozen.conds[c].copy()
+    r0, s0 = vj.backward(frozen, x, lam, True)
+    assert r0 <= vj.kf and s0 <= vj.ks
+    try:
+        frozen.conds[c][7, -1] *= 1 + 1e-10
+        r, s = vj.backward(frozen, x, lam, True)
+    finally:
+        frozen.conds[c] = keep
+    print(f"vector judge, d entry * (1 + 1e-10): rhs {r:.3g}u solve {s:.3g}u")
+    assert r > vj.kf
