@@ -508,5 +508,111 @@ def pose3_init_structure(arrays: A.ProblemArrays):
     return ef[:n], et[:n], [adj[ap[i]:ap[i + 1]].tolist() for i in range(P + 1)]
 
 
+# ---- Pose2 initialization (include/gsx.h: lago) ----------------------------------------------------------------------
+def _n_pose2(arrays) -> int:
+    return int(np.count_nonzero(arrays.var_types == A.VAR_POSE2))
+
+
+def _given(given):
+    g = None if given is None else np.ascontiguousarray(given, dtype=np.float64)
+    return g, (None if g is None else A._dptr(g)), C.c_int64(0 if g is None else g.size)
+
+
+def lago_initialize(arrays: A.ProblemArrays, use_odometric_path: bool = True, given=None, device: int = 0) -> np.ndarray:
+    """gsx_lago_initialize: packed Values of `arrays`."""
+    f = load().gsx_lago_initialize
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    out = np.zeros(int(arrays.state_offsets()[-1]))
+    g, gp, gn = _given(given)
+    st = f(C.byref(desc), C.c_int32(int(use_odometric_path)), gp, gn, C.c_int32(device), A._dptr(out), C.c_int64(out.size))
+    _raise_init(st, "gsx_lago_initialize")
+    return out
+
+
+def lago_initialize_with_guess(arrays: A.ProblemArrays, given, device: int = 0) -> np.ndarray:
+    """gsx_lago_initialize_with_guess: packed Values of `arrays`, (x, y) of `given` and lago's theta."""
+    f = load().gsx_lago_initialize_with_guess
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    out = np.zeros(int(arrays.state_offsets()[-1]))
+    g, gp, gn = _given(given)
+    _raise_init(f(C.byref(desc), gp, gn, C.c_int32(device), A._dptr(out), C.c_int64(out.size)),
+                "gsx_lago_initialize_with_guess")
+    return out
+
+
+def lago_initialize_orientations(arrays: A.ProblemArrays, use_odometric_path: bool = True, device: int = 0) -> np.ndarray:
+    """gsx_lago_initialize_orientations: one unwrapped angle per POSE2 variable, in the order of `arrays`."""
+    f = load().gsx_lago_initialize_orientations
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    out = np.zeros(_n_pose2(arrays))
+    st = f(C.byref(desc), C.c_int32(int(use_odometric_path)), C.c_int32(device), A._dptr(out), C.c_int64(out.size))
+    _raise_init(st, "gsx_lago_initialize_orientations")
+    return out
+
+
+def lago_structure(arrays: A.ProblemArrays, use_odometric_path: bool = True) -> dict:
+    """gsx_lago_structure (host): edge_from, edge_to, parent, delta (node P = the anchor), tree_ids, chord_ids, max_depth."""
+    f = load().gsx_lago_structure
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    ne, nt, depth = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    odo = C.c_int32(int(use_odometric_path))
+    _raise_init(f(C.byref(desc), odo, C.byref(ne), None, None, None, None, None, None, None, None), "gsx_lago_structure")
+    n, P = ne.value, _n_pose2(arrays)
+    ef, et, ti, ci = (np.zeros(max(n, 1), np.int32) for _ in range(4))
+    parent, delta = np.zeros(P + 1, np.int32), np.zeros(P + 1)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _raise_init(f(C.byref(desc), odo, C.byref(ne), ip(ef), ip(et), ip(parent), A._dptr(delta), C.byref(nt), ip(ti), ip(ci),
+                  C.byref(depth)), "gsx_lago_structure")
+    return dict(edge_from=ef[:n], edge_to=et[:n], parent=parent, delta=delta, tree_ids=ti[:nt.value],
+                chord_ids=ci[:n - nt.value], max_depth=int(depth.value))
+
+
+def lago_thetas_to_root(parent, delta, device: int = 0) -> np.ndarray:
+    """gsx_lago_thetas_to_root: the sum of `delta` from every node of the forest `parent` (a root: itself) to its root."""
+    f = load().gsx_lago_thetas_to_root
+    f.restype = C.c_int32
+    p = np.ascontiguousarray(parent, dtype=np.int32)
+    d = np.ascontiguousarray(delta, dtype=np.float64)
+    if p.shape != d.shape or p.ndim != 1:
+        raise ValueError("parent and delta: one entry per node")
+    out = np.zeros(max(p.size, 1))
+    _raise_init(f(p.ctypes.data_as(C.POINTER(C.c_int32)), A._dptr(d), C.c_int64(p.size), C.c_int32(device), A._dptr(out)),
+                "gsx_lago_thetas_to_root")
+    return out[:p.size]
+
+
+def lago_regularized_measurements(arrays: A.ProblemArrays, use_odometric_path: bool = True, device: int = 0) -> np.ndarray:
+    """gsx_lago_regularized_measurements: the regularized deltaTheta of every pose-graph edge, in edge order."""
+    f = load().gsx_lago_regularized_measurements
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    ne = C.c_int32(0)
+    g = load().gsx_lago_structure
+    g.restype = C.c_int32
+    _raise_init(g(C.byref(desc), C.c_int32(int(use_odometric_path)), C.byref(ne), None, None, None, None, None, None, None,
+                  None), "gsx_lago_structure")
+    out = np.zeros(max(ne.value, 1))
+    st = f(C.byref(desc), C.c_int32(int(use_odometric_path)), C.c_int32(device), A._dptr(out), C.c_int64(ne.value))
+    _raise_init(st, "gsx_lago_regularized_measurements")
+    return out[:ne.value]
+
+
+LAGO_TIMING_NAMES = ("orientation_analysis_host_ms", "theta_to_root_ms", "orientation_blocks_ms", "orientation_solve_ms",
+                     "pose_analysis_host_ms", "pose_blocks_ms", "pose_solve_ms", "compose_ms")
+
+
+def lago_timings() -> dict:
+    """gsx_lago_timings: the stage times of the last lago call of the process."""
+    f = load().gsx_lago_timings
+    f.restype = C.c_int32
+    out = np.zeros(len(LAGO_TIMING_NAMES))
+    _raise_init(f(A._dptr(out), C.c_int32(out.size)), "gsx_lago_timings")
+    return dict(zip(LAGO_TIMING_NAMES, (float(x) for x in out)))
+
+
 def product_backend(arrays: A.ProblemArrays, device: int = 0) -> ProductBackend:
     return ProductBackend(arrays, device)

@@ -215,6 +215,46 @@ void lower_relaxed(const gsx_problem_desc* d, const PoseGraph& G, OwnedDesc& out
 // variables, the pose-graph edges of non-zero weight as between factors with their own noise, a Unit prior on the anchor.
 void lower_anchor_graph(const gsx_problem_desc* d, const PoseGraph& G, OwnedDesc& out, std::vector<int>& var_of_node);
 
+// ---- Pose2 initialization: lago (lago_graph.cpp: host lowering and trees; lago.hip: device work) --------------------------
+// The pose graph of initialize::buildPoseGraph<Pose2> (gtsam/slam/InitializePose.h:36-52) over the POSE2 variables of a
+// description, the spanning tree of lago::findOdometricPath / findMinimumSpanningTree (gtsam/slam/lago.cpp:202-260) and
+// the tree / chord split of lago::getSymbolicGraph (:101-138).  node = rank of the variable among the description's POSE2
+// variables, the anchor (kAnchorKey) last.
+struct LagoGraph {
+  int n_poses = 0;                   // POSE2 variables of the description; the anchor is node n_poses
+  std::vector<int> pose_var;         // node -> variable index in the description
+  std::vector<int> node_of_var;      // variable -> node, -1: not a POSE2 variable
+  std::vector<uint64_t> key;         // node -> key (the anchor's last)
+  std::vector<char> touched;         // node -> some used factor holds it
+  bool all_touched = true;           // every POSE2 variable is held by a used factor
+  // edges in factor order (a prior is an edge from the anchor): the reference's pose2Graph
+  std::vector<int> from, to, factor;
+  std::vector<double> meas;          // 3 per edge: dx, dy, measured().theta()
+  std::vector<double> sigma;         // 3 per edge: the sigmas of its Diagonal model
+  // the tree (lago_tree)
+  std::vector<int> parent;           // node -> parent node; the anchor: itself; -1: no entry in the PredecessorMap
+  std::vector<double> delta;         // node -> signed deltaTheta of the edge parent -> node (deltaThetaMap), 0 without one
+  std::vector<int> tree_ids, chord_ids;  // edges, each list in factor order (spanningTreeIds, chordsIds)
+  std::vector<char> is_chord;        // edge -> chord
+  int max_depth = 0;                 // edges on the longest path from a node to the anchor
+  bool anchored = true;              // false: the node the odometric path attaches to the anchor carries no prior
+};
+// GSX_E_INVALID: malformed description, anchor-key collision, a Gaussian or robust model or a sigma that is not positive on
+// a used factor
+gsx_status build_lago_graph(const gsx_problem_desc* d, LagoGraph& G, std::string& err);
+// GSX_E_INVALID where the reference's tree.at(key) throws
+gsx_status lago_tree(LagoGraph& G, bool use_odometric_path, std::string& err);
+// The orientation system of buildLinearOrientationGraph (:165-199) with theta_anchor = 0 substituted: the touched poses as
+// VECTOR(1) variables in key order; per edge one 1 x 3 GSX_F_LINEAR block, or 1 x 2 for an edge from the anchor (zeros
+// here: lago_orientation_blocks_kernel writes them).  var_of_node: node -> variable (-1: untouched or the anchor).
+void lower_lago_orientations(const gsx_problem_desc* d, const LagoGraph& G, OwnedDesc& out, std::vector<int>& var_of_node);
+// The pose system of computePoses (:308-356): the touched poses and the anchor as VECTOR(3) variables in key order; one
+// 3 x 7 block per edge (zeros here: lago_pose_blocks_kernel writes them), then the anchor's prior, whitened by
+// Variances(1e-6, 1e-6, 1e-8).
+void lower_lago_poses(const gsx_problem_desc* d, const LagoGraph& G, OwnedDesc& out, std::vector<int>& var_of_node);
+// depth of every node of a forest given by parent links (root: parent[i] == i); false: an index out of range or a cycle
+bool forest_depths(const int32_t* parent, int64_t n, std::vector<int>& depth, int* max_depth);
+
 // seams of initialize.hip into a handle (solver.hip); the pointers are device memory on the handle's device
 double* handle_jacobian_pool(gsx_context* h);   // the [A b] blocks, factor f at HostProblem::f_jac_off[f]
 double* handle_values(gsx_context* h);          // packed Values

@@ -822,6 +822,116 @@ class InitializePose3:
         return Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, packed)
 
 
+class lago:
+    """namespace lago (gtsam/slam/lago.h) on the device: a spanning tree on the host, then the cumulative orientations, the
+    regularized orientation system, the pose system and the composition on the device (include/gsx.h: gsx_lago_*)."""
+
+    kAnchorKey = A.ANCHOR_KEY
+
+    @staticmethod
+    def buildPose2graph(graph) -> "NonlinearFactorGraph":
+        """initialize::buildPoseGraph<Pose2> (InitializePose.h:36-52): the BetweenFactor<Pose2> of the graph, and every
+        PriorFactor<Pose2> as a between factor from the anchor key with the prior's noise."""
+        out = NonlinearFactorGraph()
+        for f in graph.factors:
+            if f is None or getattr(f, "value_type", None) != A.VAR_POSE2:
+                continue
+            if f.ftype == A.F_BETWEEN:
+                out.add(f)
+            elif f.ftype == A.F_PRIOR:
+                out.add(BetweenFactor(A.ANCHOR_KEY, f.keys_[0], Pose2.from_state(f.meas), f.noise))
+        return out
+
+    @staticmethod
+    def _lower(pose2Graph, given: Optional["Values"] = None):
+        """The arrays of include/gsx.h for a graph of buildPose2graph: its keys as POSE2 variables, a between factor from
+        the anchor as the prior it came from; and `given` packed in that order (None without one)."""
+        keys = sorted({k for f in pose2Graph.factors for k in f.keys_} - {A.ANCHOR_KEY})
+        values = Values()
+        for k in keys:
+            values.insert(k, given.at(k) if given is not None else Pose2())
+        g = NonlinearFactorGraph()
+        for f in pose2Graph.factors:
+            if f.ftype != A.F_BETWEEN or getattr(f, "value_type", None) != A.VAR_POSE2:
+                raise ValueError("lago: not a graph of buildPoseGraph<Pose2>")
+            if f.keys_[0] == A.ANCHOR_KEY:
+                g.add(PriorFactor(f.keys_[1], Pose2.from_state(f.meas), f.noise))
+            else:
+                g.add(f)
+        arr = g.to_arrays(values)
+        return arr, keys, (arr.values if given is not None else None)
+
+    @staticmethod
+    def findMinimumSpanningTree(pose2Graph) -> Dict[Key, Key]:
+        """lago::findMinimumSpanningTree (lago.cpp:229-260): the PredecessorMap {key: parent key}, the anchor its own."""
+        from . import _lib
+        arr, keys, _ = lago._lower(pose2Graph)
+        names = keys + [A.ANCHOR_KEY]
+        parent = _lib.lago_structure(arr, False)["parent"]
+        return {names[i]: names[p] for i, p in enumerate(parent) if p >= 0}
+
+    @staticmethod
+    def getSymbolicGraph(tree, g):
+        """lago::getSymbolicGraph (lago.cpp:101-138) for any PredecessorMap: (spanningTreeIds, chordsIds, deltaThetaMap).
+        Ids count every factor of g; a missing key raises KeyError as tree.at does."""
+        spanningTreeIds, chordsIds, deltaThetaMap = [], [], {}
+        i = 0
+        for f in g.factors:
+            if f is not None and len(f.keys_) == 2:
+                if f.ftype != A.F_BETWEEN or getattr(f, "value_type", None) != A.VAR_POSE2:
+                    continue   # (the reference's `continue` skips its id++ as well)
+                key1, key2 = f.keys_
+                deltaTheta = float(f.meas[2])
+                if deltaTheta > math.pi or deltaTheta <= -math.pi:   # measured().theta()
+                    deltaTheta = math.atan2(math.sin(deltaTheta), math.cos(deltaTheta))
+                if tree[key1] == key2:
+                    deltaThetaMap.setdefault(key1, -deltaTheta)
+                    spanningTreeIds.append(i)
+                elif tree[key2] == key1:
+                    deltaThetaMap.setdefault(key2, deltaTheta)
+                    spanningTreeIds.append(i)
+                else:
+                    chordsIds.append(i)
+            i += 1
+        return spanningTreeIds, chordsIds, deltaThetaMap
+
+    @staticmethod
+    def computeThetasToRoot(deltaThetaMap, tree) -> Dict[Key, float]:
+        """lago::computeThetasToRoot (lago.cpp:82-98) on the device (gsx_lago_thetas_to_root)."""
+        from . import _lib
+        keys = sorted(tree)
+        index = {k: i for i, k in enumerate(keys)}
+        parent = np.array([index[tree[k]] for k in keys], dtype=np.int32)
+        delta = np.array([0.0 if tree[k] == k else deltaThetaMap[k] for k in keys])
+        theta = _lib.lago_thetas_to_root(parent, delta)
+        return {k: float(theta[index[k]]) for k in keys if k in deltaThetaMap or tree[k] == k}
+
+    @staticmethod
+    def initializeOrientations(graph, useOdometricPath=True) -> Dict[Key, np.ndarray]:
+        """lago::initializeOrientations (lago.cpp:297-305): {key: [theta]}, not wrapped, the anchor's (0) included as in
+        the reference's VectorValues."""
+        from . import _lib
+        arr, keys, _ = lago._lower(lago.buildPose2graph(graph))
+        theta = _lib.lago_initialize_orientations(arr, bool(useOdometricPath))
+        out = {k: np.array([t]) for k, t in zip(keys, theta)}
+        out[A.ANCHOR_KEY] = np.array([0.0])
+        return out
+
+    @staticmethod
+    def initialize(graph, useOdometricPathOrInitialGuess=True) -> "Values":
+        """lago::initialize(graph, useOdometricPath = true) (lago.cpp:375-388) and lago::initialize(graph, initialGuess)
+        (:391-409): with a Values the poses keep its x and y and take lago's orientation (odometric tree)."""
+        from . import _lib
+        pg = lago.buildPose2graph(graph)
+        if isinstance(useOdometricPathOrInitialGuess, Values):
+            arr, _, given = lago._lower(pg, useOdometricPathOrInitialGuess)
+            packed = _lib.lago_initialize_with_guess(arr, given)
+        else:
+            arr, _, _ = lago._lower(pg)
+            packed = _lib.lago_initialize(arr, bool(useOdometricPathOrInitialGuess))
+        return Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, packed)
+
+
 def _make_backend(arrays, backend_factory):
     if backend_factory is None:
         from ._lib import product_backend

@@ -759,6 +759,70 @@ gsx_status gsx_pose3_init_structure(const gsx_problem_desc* desc, int32_t* n_edg
  * events on the internal handle's stream; a stage that did not run is 0. */
 gsx_status gsx_pose3_init_timings(double* out_ms, int32_t n);
 
+/* ---- Pose2 initialization: lago (gtsam/slam/lago.{h,cpp}, gtsam/slam/InitializePose.h) -------------------------------------
+ * Linear approximation for graph optimization: (1) a spanning tree of the pose graph, (2) the cumulative orientation of
+ * every pose along the tree, which removes the 2 k pi wrap-around of every loop-closing edge (chord), (3) one linear
+ * least-squares solve in the orientations, (4) one in the full poses.  The tree is built on the host; everything from (2) on
+ * runs on the device, the two solves on internal handles (direct solver, one device) that the call builds and frees.
+ * What is used of `desc`: GSX_F_BETWEEN on two POSE2 variables and GSX_F_PRIOR on a POSE2 variable; every other factor is
+ * ignored (a prior on a VECTOR(1) orientation included), as buildPoseGraph drops it (InitializePose.h:36-52).  A prior
+ * becomes an edge from the ANCHOR (key 99999999) with the prior's noise; a variable of `desc` with that key:
+ * GSX_E_INVALID.  The measured angle is measured().theta(): kept as stored when inside (-pi, pi], else atan2(sin, cos).
+ * Noise: the reference needs a noiseModel::Diagonal (lago.cpp:142-162, :344-348): GSX_NOISE_UNIT / ISOTROPIC / DIAGONAL /
+ * CONSTRAINED are taken, GSX_NOISE_GAUSSIAN or any robust kind on a used factor is GSX_E_INVALID (the reference throws
+ * invalid_argument), and so is a sigma that is not positive (a stated limit: the reference would carry a constrained row).
+ * Nodes: the POSE2 variables of `desc` in its order (0 .. P-1), the anchor = P; edges: the used factors in factor order.
+ * The tree: use_odometric_path != 0: findOdometricPath (lago.cpp:202-226) — the first edge between consecutive keys gives a
+ * node its parent, the smallest key seen is attached to the anchor, an edge from the anchor is never consecutive;
+ * else findMinimumSpanningTree (:229-260) — Kruskal with unit weights in factor order, then the reference's stack-driven
+ * walk from the anchor.  GSX_E_INVALID where the reference's tree.at(key) throws: a used pose without a tree entry (a key
+ * gap on the odometric path; a pose not joined to the anchor in MST mode, e.g. no prior).  On the odometric path the pose
+ * attached to the anchor may carry no prior (the reference's deltaThetaMap.at throws there): the orientation system has no
+ * row that fixes its gauge and the numeric calls return GSX_E_INDETERMINATE; so does a failed factorization.
+ * The anchor's orientation prior has sigma 0 in the reference (:43-44, :196-197); here theta_anchor = 0 is substituted
+ * before the solve (the same solution): the orientation system has one scalar variable per used pose and an edge from the
+ * anchor is a unary row.  The pose system has the used poses and the anchor as 3-dimensional variables and the anchor's
+ * prior Variances(1e-6, 1e-6, 1e-8) (:45-46, :355).
+ * values_out is packed like gsx_get_values for `desc`; the angle of a POSE2 state is written as Pose2(x, y, theta).theta()
+ * returns it, in (-pi, pi].  A variable that is not POSE2, or a POSE2 variable no used factor holds, is copied from `given`
+ * (GSX_E_INVALID when there is one and given == NULL).  GSX_E_NO_DEVICE: no usable device (every call but
+ * gsx_lago_structure); every GSX_E_INVALID above comes before a device is touched. */
+/* lago::initialize(graph, useOdometricPath) (lago.cpp:375-388); given may be NULL (see above) */
+gsx_status gsx_lago_initialize(const gsx_problem_desc* desc, int32_t use_odometric_path, const double* given,
+                               int64_t n_given, int32_t device, double* values_out, int64_t n_out);
+/* lago::initializeOrientations (:297-305): one double per POSE2 variable of desc, in its order, NOT wrapped (the
+ * reference's VectorValues); 0 for a pose no used factor holds.  n_out = the number of POSE2 variables. */
+gsx_status gsx_lago_initialize_orientations(const gsx_problem_desc* desc, int32_t use_odometric_path, int32_t device,
+                                            double* theta_out, int64_t n_out);
+/* lago::initialize(graph, initialGuess) (:391-409): the odometric tree; x and y of every pose are those of `given`, bit
+ * for bit, theta is lago's. */
+gsx_status gsx_lago_initialize_with_guess(const gsx_problem_desc* desc, const double* given, int64_t n_given, int32_t device,
+                                          double* values_out, int64_t n_out);
+/* host only, needs no device: the pose graph, the tree and the split of getSymbolicGraph (:101-138).  edge_from / edge_to
+ * [*n_edges] (call once with every array NULL for *n_edges; the tree is then not built); parent [P + 1]: the parent node,
+ * the anchor its own, -1 for a pose without a tree entry; delta [P + 1]: the signed deltaTheta of the edge parent -> node,
+ * inserted once (a duplicate does not overwrite it), 0 without one; tree_ids [*n_tree] and chord_ids [*n_edges - *n_tree]:
+ * edge indices, each list in factor order (room for *n_edges each is enough); *max_depth: edges on the longest path from a
+ * pose to the anchor.  Any pointer may be NULL. */
+gsx_status gsx_lago_structure(const gsx_problem_desc* desc, int32_t use_odometric_path, int32_t* n_edges, int32_t* edge_from,
+                              int32_t* edge_to, int32_t* parent, double* delta, int32_t* n_tree, int32_t* tree_ids,
+                              int32_t* chord_ids, int32_t* max_depth);
+/* lago::computeThetasToRoot (:56-98) on a forest of n nodes given by parent links (a root: parent[i] == i, its delta is
+ * ignored): out[i] = the sum of delta over the path from i to its root.  Pointer jumping: ceil(log2(max depth + 1)) launches
+ * enqueued back to back, double-buffered.  The summation order differs from the reference's walk: per node
+ * |out - reference| <= depth * 2^-53 * sum |delta| over its path.  GSX_E_INVALID: a link out of range or a cycle. */
+gsx_status gsx_lago_thetas_to_root(const int32_t* parent, const double* delta, int64_t n, int32_t device, double* out);
+/* the regularized deltaTheta of every edge, in edge order (buildLinearOrientationGraph, :165-199): a tree edge keeps its
+ * measurement, a chord takes dtheta - 2 pi round((dtheta + theta_root[key1] - theta_root[key2]) / 2 pi).  n_out = n_edges. */
+gsx_status gsx_lago_regularized_measurements(const gsx_problem_desc* desc, int32_t use_odometric_path, int32_t device,
+                                             double* out, int64_t n_out);
+/* Stage times (ms) of the LAST lago call of the process (not thread-safe; for tools/lago_probe.py), n = 8: [0] host:
+ * lowering + ordering + symbolic analysis + upload of the orientation system; [1] the lago_theta_to_root_kernel rounds;
+ * [2] lago_orientation_blocks_kernel; [3] the orientation solve; [4] host: as [0] for the pose system; [5]
+ * lago_pose_blocks_kernel; [6] the pose solve; [7] lago_compose_kernel.  [1]-[3], [5]-[7] are HIP events on the internal
+ * handles' streams; a stage that did not run is 0. */
+gsx_status gsx_lago_timings(double* out_ms, int32_t n);
+
 /* ---- dense kernel exposed for unit parity (gtsam/base/cholesky.cpp:108-159) -- */
 /* In-place partial Cholesky of an n x n column-major symmetric matrix (upper
  * triangle significant, like the reference): on return the first nfrontal rows
