@@ -128,6 +128,17 @@ class InitPose3Params(C.Structure):
                 ("single_iter", C.c_int32)]
 
 
+class TriangulationParams(C.Structure):
+    """gsx_triangulation_params: TriangulationParameters + the arguments of triangulatePoint3 (triangulation.h:424-430,562-607)."""
+    _fields_ = [("rank_tol", C.c_double), ("optimize", C.c_int32), ("use_lost", C.c_int32), ("noise_kind", C.c_int32),
+                ("noise", C.c_double * 5), ("landmark_distance_threshold", C.c_double),
+                ("dynamic_outlier_rejection_threshold", C.c_double), ("safe", C.c_int32)]
+
+
+# TriangulationResult::Status (triangulation.h:644) + the Cal3Bundler::calibrate failure
+TRI_VALID, TRI_DEGENERATE, TRI_BEHIND_CAMERA, TRI_OUTLIER, TRI_FAR_POINT, TRI_CALIBRATION_FAILED = range(6)
+CAMERA_POSE3_CAL3_S2, CAMERA_CAL3BUNDLER = range(2)
+
 ANCHOR_KEY = 99999999   # initialize::kAnchorKey (gtsam/slam/InitializePose.h:30)
 
 

@@ -614,5 +614,82 @@ def lago_timings() -> dict:
     return dict(zip(LAGO_TIMING_NAMES, (float(x) for x in out)))
 
 
+# ---- landmark triangulation (include/gsx.h: gsx_triangulate*) -----------------------------------------------------------
+def triangulation_params_default() -> A.TriangulationParams:
+    p = A.TriangulationParams()
+    f = load().gsx_triangulation_params_default
+    f.restype = None
+    f(C.byref(p))
+    return p
+
+
+def triangulate(camera_kind: int, cameras, calibrations, track_ptr, obs_camera, obs_xy, params: A.TriangulationParams = None,
+                device: int = 0, with_counts: bool = False):
+    """gsx_triangulate: (points (n, 3), statuses (n,)[, LM counts (n, 2)]).  cameras (n_cam, 12) Pose3 states with
+    calibrations (1 or n_cam, 5), or (n_cam, 17) camera states with calibrations None."""
+    f = load().gsx_triangulate
+    f.restype = C.c_int32
+    width = 17 if camera_kind == A.CAMERA_CAL3BUNDLER else 12
+    cam = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, width)
+    cal = None if calibrations is None else np.ascontiguousarray(calibrations, dtype=np.float64).reshape(-1, 5)
+    ptr = np.ascontiguousarray(track_ptr, dtype=np.int64)
+    oc = np.ascontiguousarray(obs_camera, dtype=np.int32)
+    xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
+    if ptr.size < 1 or oc.size != xy.shape[0] or int(ptr[-1]) != oc.size:
+        raise ValueError("track_ptr must index obs_camera / obs_xy")
+    n = ptr.size - 1
+    points, status, counts = np.zeros((max(n, 1), 3)), np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 2), np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    st = f(C.c_int32(camera_kind), A._dptr(cam) if cam.size else None, C.c_int32(cam.shape[0]),
+           None if cal is None or cal.size == 0 else A._dptr(cal), C.c_int32(0 if cal is None else cal.shape[0]),
+           ptr.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(n), ip(oc) if oc.size else None,
+           A._dptr(xy) if xy.size else None, None if params is None else C.byref(params), C.c_int32(device),
+           A._dptr(points), ip(status), ip(counts) if with_counts else None)
+    _raise_init(st, "gsx_triangulate")
+    return (points[:n], status[:n], counts[:n]) if with_counts else (points[:n], status[:n])
+
+
+def triangulation_tracks(arrays: A.ProblemArrays):
+    """gsx_triangulation_tracks (host): (landmark variable indices, track_ptr, factor index per observation)."""
+    f = load().gsx_triangulation_tracks
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    nl, no = C.c_int32(0), C.c_int64(0)
+    _raise_init(f(C.byref(desc), C.byref(nl), C.byref(no), None, None, None), "gsx_triangulation_tracks")
+    lm, ptr, of = np.zeros(max(nl.value, 1), np.int32), np.zeros(nl.value + 1, np.int64), np.zeros(max(no.value, 1), np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _raise_init(f(C.byref(desc), C.byref(nl), C.byref(no), ip(lm), ptr.ctypes.data_as(C.POINTER(C.c_int64)), ip(of)),
+                "gsx_triangulation_tracks")
+    return lm[:nl.value], ptr, of[:no.value]
+
+
+def triangulate_landmarks(arrays: A.ProblemArrays, values=None, params: A.TriangulationParams = None, device: int = 0):
+    """gsx_triangulate_landmarks: (packed Values with the VALID landmarks overwritten, status per landmark in the order of
+    triangulation_tracks)."""
+    f = load().gsx_triangulate_landmarks
+    f.restype = C.c_int32
+    desc = arrays.desc()
+    v = np.ascontiguousarray(arrays.values if values is None else values, dtype=np.float64)
+    out = np.zeros(max(v.size, 1))
+    status = np.zeros(max(arrays.n_vars, 1), np.int32)
+    nl = C.c_int32(0)
+    st = f(C.byref(desc), A._dptr(v), C.c_int64(v.size), None if params is None else C.byref(params), C.c_int32(device),
+           A._dptr(out), status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nl))
+    _raise_init(st, "gsx_triangulate_landmarks")
+    return out[:v.size], status[:nl.value]
+
+
+TRIANGULATE_TIMING_NAMES = ("classes_host_ms", "cameras_ms", "short_tracks_ms", "long_tracks_ms", "total_host_ms")
+
+
+def triangulate_timings() -> dict:
+    """gsx_triangulate_timings: the stage times of the last triangulation call of the process."""
+    f = load().gsx_triangulate_timings
+    f.restype = C.c_int32
+    out = np.zeros(len(TRIANGULATE_TIMING_NAMES))
+    _raise_init(f(A._dptr(out), C.c_int32(out.size)), "gsx_triangulate_timings")
+    return dict(zip(TRIANGULATE_TIMING_NAMES, (float(x) for x in out)))
+
+
 def product_backend(arrays: A.ProblemArrays, device: int = 0) -> ProductBackend:
     return ProductBackend(arrays, device)

@@ -932,6 +932,183 @@ class lago:
         return Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, packed)
 
 
+# ---- triangulation (gtsam/geometry/triangulation.h) on the device: include/gsx.h gsx_triangulate* --------------------------
+class TriangulationUnderconstrainedException(RuntimeError):
+    """triangulation.h:42-48"""
+
+    def __init__(self):
+        super().__init__("Triangulation Underconstrained Exception.")
+
+
+class TriangulationCheiralityException(RuntimeError):
+    """triangulation.h:50-56"""
+
+    def __init__(self):
+        super().__init__("Triangulation Cheirality Exception: The resulting landmark is behind one or more cameras.")
+
+
+class PinholeCameraCal3_S2:
+    """PinholeCamera<Cal3_S2> (gtsam/geometry/PinholeCamera.h) as far as triangulation needs it."""
+
+    def __init__(self, pose: Optional[Pose3] = None, K: Optional[Cal3_S2] = None):
+        self.pose_, self.K_ = pose if pose is not None else Pose3(), K if K is not None else Cal3_S2()
+
+    def pose(self):
+        return self.pose_
+
+    def calibration(self):
+        return self.K_
+
+    def project(self, point):
+        """PinholeCamera::project: raises ValueError behind the camera (CheiralityException)."""
+        q = self.pose_.transformTo(np.asarray(point, dtype=float))
+        if q[2] <= 0:
+            raise ValueError("CheiralityException: landmark behind camera")
+        fx, fy, s, u0, v0 = self.K_.v
+        x, y = q[0] / q[2], q[1] / q[2]
+        return np.array([fx * x + s * y + u0, fy * y + v0])
+
+
+class TriangulationParameters:
+    """TriangulationParameters (triangulation.h:562-607), the reference's constructor order and defaults."""
+
+    def __init__(self, rankTolerance=1.0, enableEPI=False, landmarkDistanceThreshold=-1.0,
+                 dynamicOutlierRejectionThreshold=-1.0, useLOST=False, noiseModel=None):
+        self.rankTolerance, self.enableEPI = float(rankTolerance), bool(enableEPI)
+        self.landmarkDistanceThreshold = float(landmarkDistanceThreshold)
+        self.dynamicOutlierRejectionThreshold = float(dynamicOutlierRejectionThreshold)
+        self.useLOST, self.noiseModel = bool(useLOST), noiseModel
+
+    def c_params(self, safe=True) -> A.TriangulationParams:
+        return _triangulation_c_params(self.rankTolerance, self.enableEPI, self.noiseModel, self.useLOST,
+                                       self.landmarkDistanceThreshold, self.dynamicOutlierRejectionThreshold, safe)
+
+
+def _triangulation_c_params(rank_tol, optimize, model, useLOST, far=-1.0, outlier=-1.0, safe=False) -> A.TriangulationParams:
+    p = A.TriangulationParams()
+    p.rank_tol, p.optimize, p.use_lost, p.safe = float(rank_tol), int(bool(optimize)), int(bool(useLOST)), int(bool(safe))
+    p.landmark_distance_threshold, p.dynamic_outlier_rejection_threshold = float(far), float(outlier)
+    p.noise_kind = -1
+    if model is not None:
+        if model.dim() != 2:
+            raise ValueError("TriangulationFactor must be created with 2-dimensional noise model.")
+        if model.params.size > 5:
+            raise ValueError("triangulation: noise model not supported")
+        p.noise_kind = int(model.kind)
+        for i, v in enumerate(model.params):
+            p.noise[i] = float(v)
+    return p
+
+
+class TriangulationResult:
+    """TriangulationResult (triangulation.h:642-698): an optional point and the reason why it is missing."""
+    VALID, DEGENERATE, BEHIND_CAMERA, OUTLIER, FAR_POINT = range(5)
+    CALIBRATION_FAILED = 5   # Cal3Bundler::calibrate did not converge (the reference's runtime_error)
+
+    def __init__(self, status, point=None):
+        self.status = int(status)
+        self.point = None if point is None or self.status != self.VALID else np.array(point, dtype=float)
+
+    def valid(self): return self.status == self.VALID
+    def degenerate(self): return self.status == self.DEGENERATE
+    def outlier(self): return self.status == self.OUTLIER
+    def farPoint(self): return self.status == self.FAR_POINT
+    def behindCamera(self): return self.status == self.BEHIND_CAMERA
+
+    def get(self):
+        if self.point is None:
+            raise RuntimeError("TriangulationResult has no value")
+        return self.point
+
+    def __repr__(self):
+        return f"point = {self.point}" if self.point is not None else f"no point, status = {self.status}"
+
+
+def _camera_arrays(cameras_or_poses, sharedCal):
+    """(camera_kind, cameras, calibrations) of gsx_triangulate from poses + a shared Cal3_S2 / Cal3Bundler, or a camera set"""
+    if sharedCal is not None:
+        poses = list(cameras_or_poses)
+        if isinstance(sharedCal, Cal3Bundler):
+            cams = [np.concatenate([p.state(), sharedCal.vector()]) for p in poses]
+            return A.CAMERA_CAL3BUNDLER, np.array(cams).reshape(-1, 17), None
+        if not isinstance(sharedCal, Cal3_S2):
+            raise ValueError("triangulation: only Cal3_S2 and Cal3Bundler calibrations are supported")
+        return A.CAMERA_POSE3_CAL3_S2, np.array([p.state() for p in poses]).reshape(-1, 12), sharedCal.vector().reshape(1, 5)
+    cams = list(cameras_or_poses)
+    if cams and isinstance(cams[0], PinholeCameraCal3Bundler):
+        return A.CAMERA_CAL3BUNDLER, np.array([c.state() for c in cams]).reshape(-1, 17), None
+    if any(not isinstance(c, PinholeCameraCal3_S2) for c in cams):
+        raise ValueError("triangulation: only PinholeCameraCal3_S2 and PinholeCameraCal3Bundler cameras are supported")
+    return (A.CAMERA_POSE3_CAL3_S2, np.array([c.pose().state() for c in cams]).reshape(-1, 12),
+            np.array([c.calibration().vector() for c in cams]).reshape(-1, 5))
+
+
+def _triangulate_one(cameras_or_poses, sharedCal, measurements, params):
+    from . import _lib
+    kind, cams, cal = _camera_arrays(cameras_or_poses, sharedCal)
+    z = np.asarray(measurements, dtype=float).reshape(-1, 2)
+    if z.shape[0] != cams.shape[0]:
+        raise ValueError("triangulation: one measurement per camera")
+    n = cams.shape[0]
+    pts, st = _lib.triangulate(kind, cams, cal, np.array([0, n], np.int64), np.arange(n, dtype=np.int32), z, params)
+    return pts[0], int(st[0])
+
+
+def triangulatePoint3(*args, **kw):
+    """triangulatePoint3(poses, sharedCal, measurements, rank_tol=1e-9, optimize=False, model=None, useLOST=False)
+    (triangulation.h:424-475) and its camera-set form triangulatePoint3(cameras, measurements, rank_tol, ...) (:491-549).
+    Raises TriangulationUnderconstrainedException / TriangulationCheiralityException."""
+    names = ("rank_tol", "optimize", "model", "useLOST")
+    if len(args) >= 2 and isinstance(args[1], (Cal3_S2, Cal3Bundler)):
+        cams, cal, meas, rest = args[0], args[1], args[2] if len(args) > 2 else kw.pop("measurements"), args[3:]
+    else:
+        cams, cal, meas, rest = args[0], None, args[1] if len(args) > 1 else kw.pop("measurements"), args[2:]
+    opt = dict(rank_tol=1e-9, optimize=False, model=None, useLOST=False)
+    opt.update(dict(zip(names, rest)))
+    opt.update(kw)
+    p = _triangulation_c_params(opt["rank_tol"], opt["optimize"], opt["model"], opt["useLOST"])
+    point, status = _triangulate_one(cams, cal, meas, p)
+    if status == A.TRI_DEGENERATE:
+        raise TriangulationUnderconstrainedException()
+    if status == A.TRI_BEHIND_CAMERA:
+        raise TriangulationCheiralityException()
+    if status == A.TRI_CALIBRATION_FAILED:
+        raise RuntimeError("Cal3Bundler::calibrate fails to converge. need a better initialization")
+    return point
+
+
+def triangulatePoint3Batch(cameras, measurements, rank_tol=1e-9, optimize=False, model=None, useLOST=False):
+    """triangulatePoint3 for many measurement sets of ONE camera set in one call on the device: measurements (n, m, 2), one
+    row of m pixels per track.  Returns (points (n, 3), statuses (n,) of TriangulationResult); a track that is not VALID has
+    NaN in its point — nothing is raised per track."""
+    from . import _lib
+    kind, cams, cal = _camera_arrays(cameras, None)
+    z = np.asarray(measurements, dtype=float)
+    if z.ndim != 3 or z.shape[1] != cams.shape[0] or z.shape[2] != 2:
+        raise ValueError("triangulatePoint3Batch: measurements must be (n, number of cameras, 2)")
+    n, m = z.shape[:2]
+    return _lib.triangulate(kind, cams, cal, np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n),
+                            z.reshape(-1, 2), _triangulation_c_params(rank_tol, optimize, model, useLOST))
+
+
+def triangulateSafe(cameras, measured, params: TriangulationParameters) -> TriangulationResult:
+    """triangulateSafe(cameras, measured, params) (triangulation.h:701-758)."""
+    point, status = _triangulate_one(cameras, None, measured, params.c_params(safe=True))
+    return TriangulationResult(status, point)
+
+
+def triangulateLandmarks(graph, values: "Values", params: Optional[TriangulationParameters] = None):
+    """Every landmark of the graph's GeneralSFMFactor / GenericProjectionFactor observations triangulated at once from the
+    cameras of `values` (gsx_triangulate_landmarks): (Values with the VALID landmarks replaced, {landmark key: status})."""
+    from . import _lib
+    params = params if params is not None else TriangulationParameters()
+    arr = graph.to_arrays(values)
+    packed, status = _lib.triangulate_landmarks(arr, None, params.c_params(safe=True))
+    lm, _, _ = _lib.triangulation_tracks(arr)
+    out = Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, packed)
+    return out, {int(arr.var_keys[v]): int(s) for v, s in zip(lm, status)}
+
+
 def _make_backend(arrays, backend_factory):
     if backend_factory is None:
         from ._lib import product_backend

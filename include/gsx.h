@@ -823,6 +823,77 @@ gsx_status gsx_lago_regularized_measurements(const gsx_problem_desc* desc, int32
  * handles' streams; a stage that did not run is 0. */
 gsx_status gsx_lago_timings(double* out_ms, int32_t n);
 
+/* ---- Landmark triangulation (gtsam/geometry/triangulation.{h,cpp}) -----------------------------------------------------------
+ * triangulatePoint3 (DLT or LOST, optionally refined by LM on the one Point3) and triangulateSafe for MANY tracks at once: a
+ * track is the list of (camera, pixel) observations of one landmark; every track is independent work for one lane (fewer than
+ * 64 observations) or one wave of the device (csrc/triangulate.hip; the per-track arithmetic is csrc/triangulate_math.h).
+ * Cameras: GSX_CAMERA_POSE3_CAL3_S2 — a Pose3 state (R row-major 9, t 3) per camera and Cal3_S2 calibrations (fx, fy, s, u0,
+ * v0), ONE shared (n_calibrations = 1) or one per camera (n_calibrations = n_cameras): PinholePose / PinholeCamera<Cal3_S2>;
+ * GSX_CAMERA_CAL3BUNDLER — the 17-double state of a GSX_VAR_CAMERA variable per camera (calibrations ignored):
+ * PinholeCamera<Cal3Bundler>, whose measurements are undistorted as undistortMeasurementInternal does (triangulation.h:
+ * 260-268; Cal3Bundler::calibrate's fixed-point loop, at most 10 rounds, tol 1e-5, Cal3Bundler.cpp:93-128).  Cal3DS2, fisheye,
+ * unified, spherical and stereo cameras are not taken.
+ * DLT (triangulateHomogeneousDLT, triangulation.cpp:27-56; DLT, base/Matrix.cpp:556-574): the rows p.x P2 - P0, p.y P2 - P1
+ * are streamed into a 4 x 4 triangle by Givens rotations and that triangle gets a one-sided Jacobi SVD — A'A is never formed;
+ * rank = singular values above rank_tol (absolute), rank < 3 is underconstrained.  LOST (triangulateLOST, :86-147): the same
+ * streaming reduction of [A b], then a column-pivoted QR of the 3 x 3 with ColPivHouseholderQR's RELATIVE rank rule (pivots
+ * above rank_tol x the largest).  Refinement (triangulateNonlinear -> optimize, :177-195): LM with lambdaInitial 1,
+ * lambdaFactor 10, maxIterations 100, absoluteErrorTol 1.0 on TriangulationFactors (gtsam/slam/TriangulationFactor.h:122-136:
+ * behind the camera a zero Jacobian and the error 2 fx (1, 1)), the decisions of gsx_lm_decide, inside the kernel.
+ * Status per track, TriangulationResult::Status (triangulation.h:644) with the cheirality checks on: a track with fewer than 2
+ * observations or an underconstrained system is DEGENERATE; a final point with transformTo(point).z <= 0 in some camera is
+ * BEHIND_CAMERA; with safe != 0 then triangulateSafe's loop (:719-745): FAR_POINT, OUTLIER.  CALIBRATION_FAILED is the
+ * reference's runtime_error of Cal3Bundler::calibrate.  Limits: a homogeneous solution with v[3] == 0 is DEGENERATE (the
+ * reference hands out a non-finite point); LOST under a robust model uses the base model's sigmas (the reference's
+ * Robust::sigmas throws).  A track that is not VALID leaves NaN in its point. */
+enum { GSX_TRI_VALID = 0, GSX_TRI_DEGENERATE = 1, GSX_TRI_BEHIND_CAMERA = 2, GSX_TRI_OUTLIER = 3, GSX_TRI_FAR_POINT = 4,
+       GSX_TRI_CALIBRATION_FAILED = 5 };
+enum { GSX_CAMERA_POSE3_CAL3_S2 = 0, GSX_CAMERA_CAL3BUNDLER = 1 };
+/* TriangulationParameters (triangulation.h:562-607) + the arguments of triangulatePoint3 (:424-430) */
+typedef struct gsx_triangulation_params {
+  double rank_tol;                 /* 1e-9 (triangulatePoint3); TriangulationParameters' own default is 1.0                */
+  int32_t optimize;                /* 0; enableEPI: refine by LM                                                          */
+  int32_t use_lost;                /* 0                                                                                   */
+  int32_t noise_kind;              /* -1: no model — unwhitened factors, LOST sigma 1e-4 (:439); else GSX_NOISE_UNIT /
+                                      ISOTROPIC / DIAGONAL / GAUSSIAN of dimension 2, robust bits allowed.
+                                      GSX_NOISE_CONSTRAINED or a sigma that is not positive: GSX_E_INVALID, the reference's
+                                      factor does not support them (TriangulationFactor.h:144)                            */
+  double noise[5];                 /* the model's parameters as in gsx_problem_desc.noise, then the robust parameter      */
+  double landmark_distance_threshold;            /* -1; <= 0: off                                                         */
+  double dynamic_outlier_rejection_threshold;    /* -1; <= 0: off; compared with the LARGEST reprojection error norm      */
+  int32_t safe;                    /* 0: triangulatePoint3 — only the underconstrained and cheirality outcomes;
+                                      1: triangulateSafe                                                                  */
+} gsx_triangulation_params;
+void gsx_triangulation_params_default(gsx_triangulation_params* p);
+/* triangulatePoint3 / triangulateSafe on n_tracks tracks.  track_ptr [n_tracks + 1] is a CSR into obs_camera (camera index)
+ * and obs_xy (2 doubles per observation).  Writes points_out [3 n_tracks] and status_out [n_tracks]; lm_counts_out (may be
+ * NULL) [2 n_tracks]: the accepted LM iterations and the trials that changed the controller, 0 without refinement.  params
+ * == NULL: the defaults.  Zero tracks: GSX_OK.  GSX_E_INVALID (before a device is touched): a camera index out of range, a
+ * malformed CSR, a refused noise model.  GSX_E_NO_DEVICE without a usable device. */
+gsx_status gsx_triangulate(int32_t camera_kind, const double* cameras, int32_t n_cameras, const double* calibrations,
+                           int32_t n_calibrations, const int64_t* track_ptr, int64_t n_tracks, const int32_t* obs_camera,
+                           const double* obs_xy, const gsx_triangulation_params* params, int32_t device, double* points_out,
+                           int32_t* status_out, int32_t* lm_counts_out);
+/* host only, needs no device: the tracks of a problem description.  The GSX_F_SFM and GSX_F_PROJECTION factors are grouped
+ * per landmark (their second key); landmarks in the order of desc, the observations of a landmark in factor order; every
+ * other factor type is ignored.  landmark_vars [*n_landmarks] variable indices, track_ptr [*n_landmarks + 1], obs_factor
+ * [*n_observations] factor indices; call once with NULL arrays for the sizes.  GSX_E_INVALID: a landmark seen by both camera
+ * kinds, a malformed factor. */
+gsx_status gsx_triangulation_tracks(const gsx_problem_desc* desc, int32_t* n_landmarks, int64_t* n_observations,
+                                    int32_t* landmark_vars, int64_t* track_ptr, int32_t* obs_factor);
+/* The practical entry: triangulate every landmark of a problem from the cameras in `values` (packed like gsx_get_values).
+ * GSX_F_SFM observations use the GSX_VAR_CAMERA variable; GSX_F_PROJECTION observations the POSE3 variable, the factor's
+ * calibration and, where present, its body_P_sensor (composed into the pose on the device).  values_out = values with the
+ * VALID landmarks overwritten; a landmark that fails keeps its input value.  status_out: one entry per landmark in the order
+ * of gsx_triangulation_tracks (room for n_vars entries always suffices); *n_landmarks_out (may be NULL) their number. */
+gsx_status gsx_triangulate_landmarks(const gsx_problem_desc* desc, const double* values, int64_t n_values,
+                                     const gsx_triangulation_params* params, int32_t device, double* values_out,
+                                     int32_t* status_out, int32_t* n_landmarks_out);
+/* Stage times (ms) of the LAST triangulation call of the process (not thread-safe; for tools/triangulate_probe.py), n = 5:
+ * [0] host: sorting the tracks into the two classes; [1] triangulate_cameras_kernel; [2] triangulate_short_kernel; [3]
+ * triangulate_long_kernel; [4] the whole call on the host clock, transfers included.  [1]-[3] are HIP events. */
+gsx_status gsx_triangulate_timings(double* out_ms, int32_t n);
+
 /* ---- dense kernel exposed for unit parity (gtsam/base/cholesky.cpp:108-159) -- */
 /* In-place partial Cholesky of an n x n column-major symmetric matrix (upper
  * triangle significant, like the reference): on return the first nfrontal rows
