@@ -18,6 +18,8 @@ import numpy as np
 GSX_OK, GSX_E_INVALID, GSX_E_NO_DEVICE, GSX_E_BAD_ORDERING, GSX_E_INDETERMINATE, GSX_E_STATE, GSX_E_NOMEM = range(7)
 VAR_VECTOR, VAR_POSE2, VAR_POSE3, VAR_CAMERA = range(4)
 F_LINEAR, F_PRIOR, F_BETWEEN, F_SFM, F_PROJECTION, F_BEARINGRANGE, F_RANGE, F_BEARING, F_STEREO, F_SFM2 = range(10)
+F_SMART_PROJECTION = 10
+SMART_MEAS_HEAD = 11   # doubles of a smart factor's meas before body_P_sensor / the pixels (include/gsx.h)
 NOISE_FORMAT_G2O, NOISE_FORMAT_TORO, NOISE_FORMAT_GRAPH, NOISE_FORMAT_COV, NOISE_FORMAT_AUTO = range(5)
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_CONSTRAINED = range(5)
 NOISE_ROBUST_HUBER, NOISE_ROBUST_TUKEY, NOISE_ROBUST_CAUCHY, NOISE_BASE_MASK = 1 << 4, 2 << 4, 3 << 4, 15
@@ -120,6 +122,15 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SmartStats(Stats):
+    """gsx_stats as gsx_get_stats writes it: Stats (the fields up to n_pcg_solves, a prefix of the C struct) followed by the
+    two counters of the smart projection factors appended at its end.  Pass THIS one to gsx_get_stats."""
+    _fields_ = [("n_smart_invalid", C.c_int64), ("n_smart_retriangulated", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in Stats._fields_ + SmartStats._fields_}
 
 
 class InitPose3Params(C.Structure):

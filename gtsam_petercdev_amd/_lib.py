@@ -242,8 +242,17 @@ class ProductBackend(A.Backend):
         self._check(self._fn("set_linear_solver")(self._h, C.c_int32(kind), C.byref(params) if params is not None else None),
                     "set_linear_solver")
 
+    def smart_points(self):
+        """SmartProjectionFactor::point() of every smart factor in graph order (gsx_smart_points): (points [n, 3] — NaN
+        unless VALID —, status [n] — A.TRI_* or -1 when the factor was never triangulated)."""
+        n = int(np.count_nonzero(self.arrays.f_type == A.F_SMART_PROJECTION))
+        pts, st = np.full((n, 3), np.nan), np.full(n, -1, np.int32)
+        self._check(self._fn("smart_points")(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)),
+                                             st.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int64(n)), "smart_points")
+        return pts, st
+
     def stats(self) -> dict:
-        s = A.Stats()
+        s = A.SmartStats()
         self._check(self._fn("get_stats")(self._h, C.byref(s)), "get_stats")
         return s.as_dict()
 

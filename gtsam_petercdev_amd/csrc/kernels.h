@@ -168,7 +168,9 @@ enum { TL_SFM = 0, TL_BETWEEN_POSE2 = 1, TL_BETWEEN_POSE3 = 2, TL_GENERIC = 3, T
        // the forms that carry body_P_sensor behind their measurement (the same kernels with a compile-time switch), and
        // GeneralSFMFactor2
        TL_PROJECTION_SENSOR = 12, TL_STEREO_SENSOR = 13, TL_RANGE_POSE2_POINT_SENSOR = 14, TL_RANGE_POSE2_POSE_SENSOR = 15,
-       TL_RANGE_POSE3_POINT_SENSOR = 16, TL_RANGE_POSE3_POSE_SENSOR = 17, TL_SFM2 = 18, kNumTypeLists = 19 };
+       TL_RANGE_POSE3_POINT_SENSOR = 16, TL_RANGE_POSE3_POSE_SENSOR = 17, TL_SFM2 = 18,
+       // SmartProjectionPoseFactor<Cal3_S2>: kernels of its own (smart.hip), and state the handle keeps (SmartDev)
+       TL_SMART = 19, kNumTypeLists = 20 };
 constexpr int kSensorListShift = TL_RANGE_POSE2_POINT_SENSOR - TL_RANGE_POSE2_POINT;  // range list -> its sensor form
 // list of a factor of type `t` whose first two variables have types vt0, vt1 and whose measurement has nmeas doubles
 // (the sensor forms are told by their length); -1: GSX_F_LINEAR, no list
@@ -186,14 +188,37 @@ inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
              (nmeas > 1 ? kSensorListShift : 0);
     case GSX_F_BEARING: return TL_BEARING;
     case GSX_F_STEREO: return nmeas > 9 ? TL_STEREO_SENSOR : TL_STEREO;
+    case GSX_F_SMART_PROJECTION: return TL_SMART;
   }
   return TL_GENERIC;
 }
+// The state of the smart projection factors of a handle (smart.hip), per smart factor in graph order ("slot"): the cameras
+// of the call in progress, and the re-triangulation cache of SmartProjectionFactor::decideIfTriangulate — the camera poses
+// of the last triangulation, its point and its status (-1: never triangulated).
+struct SmartDev {
+  const int* slot;     // per FACTOR: its slot, -1 for every other type
+  double* cams;        // slot x 8 prepared cameras (triangulate_math.h: Camera, 32 doubles)
+  double* cache;       // slot x 8 x 12: R 9, t 3 of every camera at the last triangulation
+  double* point;       // slot x 3
+  int* status;         // slot: GSX_TRI_* or -1
+  int* counters;       // [0] factors without a valid point in the last linearize; [1] factors the last call re-triangulated
+  int n;               // smart factors of the problem
+};
+// `smart` may be null when type_counts[TL_SMART] == 0
 void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
-                      const double* values, double* jac, DevStatus* status, hipStream_t st);
+                      const double* values, double* jac, DevStatus* status, hipStream_t st, const SmartDev* smart = nullptr);
 // the graph error over the type lists of launch_linearize (a kernel per list, the factor type a compile-time constant)
 void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
-                  const double* values, double* partials, int n_partials_cap, double* scalars, int slot, hipStream_t st);
+                  const double* values, double* partials, int n_partials_cap, double* scalars, int slot, hipStream_t st,
+                  const SmartDev* smart = nullptr);
+// smart.hip.  Pass one of both calls: one lane per listed factor decides re-triangulation (consulting and updating the
+// cache), triangulates, and leaves cameras, point and status in `S`.
+void launch_smart_triangulate(const DevProblem& P, const int* list, int n, const double* values, const SmartDev& S, hipStream_t st);
+// pass two of linearize: one wave per listed factor, one lane per column of [F b]; writes the factor's [A b]
+void launch_smart_linearize(const DevProblem& P, const int* list, int n, const SmartDev& S, double* jac, hipStream_t st);
+// pass two of the error: 0.5 |whitened (h - z)|^2 at the cached points, `blocks` partial sums into partials
+void launch_smart_error(const DevProblem& P, const int* list, int n, const SmartDev& S, double* partials, int blocks,
+                        hipStream_t st);
 // slice > 0: the staged kernel (doubles of LDS per wave = the largest [A b] range of 64 consecutive factors); 0: the direct one
 void launch_linear_error(const DevProblem& P, const double* jac, const double* delta, double* partials,
                          int n_partials_cap, double* scalars, int slice, hipStream_t st);

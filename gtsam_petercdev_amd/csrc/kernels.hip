@@ -594,7 +594,7 @@ __global__ void __launch_bounds__(256) linearize_sfm2_kernel(DevProblem P, const
 }
 
 void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
-                      const double* values, double* jac, DevStatus* status, hipStream_t st) {
+                      const double* values, double* jac, DevStatus* status, hipStream_t st, const SmartDev* smart) {
   auto grid = [](int n) { return dim3((n + 255) / 256); };
   // the generic family (priors, vector-space factors: few) rides in the first blocks of the first main family's launch
   const int* glist = type_lists[3];
@@ -643,6 +643,10 @@ void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeL
   run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR, true>, TL_RANGE_POSE3_POINT_SENSOR);
   run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3, true>, TL_RANGE_POSE3_POSE_SENSOR);
   run_s(linearize_sfm2_kernel, TL_SFM2);
+  if (type_counts[TL_SMART] && smart) {   // triangulate (cache consulted and updated), then marginalize the landmark
+    launch_smart_triangulate(P, type_lists[TL_SMART], type_counts[TL_SMART], values, *smart, st);
+    launch_smart_linearize(P, type_lists[TL_SMART], type_counts[TL_SMART], *smart, jac, st);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -828,7 +832,7 @@ __global__ void __launch_bounds__(256) error_list_kernel(DevProblem P, const int
 
 void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists],
                   const int type_counts[kNumTypeLists], const double* values, double* partials, int cap, double* scalars,
-                  int slot, hipStream_t st) {
+                  int slot, hipStream_t st, const SmartDev* smart) {
   // a launch per non-empty list, its blocks a share of the partial sums proportional to its factors; the sums are added in
   // list order, block order: deterministic
   long long total = 0;
@@ -836,8 +840,9 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
   // slots held back so that a list of few factors still gets its block: one per list a graph can fill.  A graph without
   // the sensor forms and GSX_F_SFM2 keeps the shares — hence the summation order, hence the bits — it had before they came
   bool new_lists = false;
-  for (int k = TL_PROJECTION_SENSOR; k < kNumTypeLists; ++k) new_lists = new_lists || type_counts[k] > 0;
-  const int held = new_lists ? kNumTypeLists : TL_PROJECTION_SENSOR;
+  for (int k = TL_PROJECTION_SENSOR; k < TL_SMART; ++k) new_lists = new_lists || type_counts[k] > 0;
+  // (likewise a graph without smart factors keeps the shares it had before TL_SMART came)
+  const int held = type_counts[TL_SMART] > 0 ? kNumTypeLists : (new_lists ? TL_SMART : TL_PROJECTION_SENSOR);
   int off = 0;
   for (int k = 0; k < kNumTypeLists; ++k) {
     const int n = type_counts[k];
@@ -865,6 +870,10 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
       case TL_RANGE_POSE3_POINT_SENSOR:
       case TL_RANGE_POSE3_POSE_SENSOR: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_SFM2: error_list_kernel<GSX_F_SFM2, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_SMART:   // triangulate at `values` (cache consulted and updated), then the reprojection errors
+        launch_smart_triangulate(P, type_lists[k], n, values, *smart, st);
+        launch_smart_error(P, type_lists[k], n, *smart, out, nb, st);
+        break;
       default: error_list_kernel<-1, -1><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
     }
     off += nb;

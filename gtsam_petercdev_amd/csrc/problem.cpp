@@ -123,6 +123,18 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
         ok = ok && nk == 3 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && tv(2) == GSX_VAR_VECTOR &&
              dv(2) == 5 && m == 2 && nmeas == 2;
         break;
+      case GSX_F_SMART_PROJECTION: {  // 2 .. 8 POSE3 keys; 11 doubles, optionally body_P_sensor (12), then 2 nk pixels
+        ok = ok && nk >= 2 && nk <= 8 && m == 2 * nk - 3 && (nmeas == 11 + 2 * nk || nmeas == 11 + 12 + 2 * nk);
+        for (int k = 0; ok && k < nk; ++k) ok = tv(k) == GSX_VAR_POSE3;
+        // SmartFactorBase "needs isotropic"; only ZERO_ON_DEGENERACY (1) of the degeneracy modes
+        const int nkind = P.f_noise_kind[f];
+        ok = ok && (nkind == GSX_NOISE_UNIT || nkind == GSX_NOISE_ISOTROPIC);
+        if (ok && P.meas[P.f_meas_ptr[f] + 10] != 1.0) {
+          err = "factor " + std::to_string(f) + ": only ZERO_ON_DEGENERACY is taken by GSX_F_SMART_PROJECTION";
+          return GSX_E_INVALID;
+        }
+        break;
+      }
       default:
         ok = false;
     }

@@ -120,6 +120,17 @@ struct gsx_context {
   DevBuf<int> d_type_list[kNumTypeLists];
   int type_count[kNumTypeLists] = {};
   DevProblem DP{};
+  // smart projection factors (kernels.h: SmartDev; smart.hip): the cameras of the call in progress and the
+  // re-triangulation cache, per smart factor in graph order.  Made — with an empty cache — by upload_problem, that is at
+  // gsx_create and gsx_update.
+  int n_smart = 0;   // (counted on the host: known without a device)
+  DevBuf<int> d_smart_slot, d_smart_status, d_smart_counters;
+  DevBuf<double> d_smart_cams, d_smart_cache, d_smart_point;
+  SmartDev SD{};
+  // counters of a call that evaluates the smart factors: [0] is the linearize's, [1] every call's
+  void smart_begin(bool linearize) {
+    if (n_smart) hipMemsetAsync(d_smart_counters.p + (linearize ? 0 : 1), 0, (linearize ? 2 : 1) * sizeof(int), stream);
+  }
   // device symbolic
   DevBuf<i64> d_fr_off, d_cmap_ptr, d_gidx_ptr, d_h_off, d_hmap_ptr, d_term_ptr;
   DevBuf<TermRec> d_terms;
@@ -488,6 +499,25 @@ gsx_status upload_problem(gsx_context* c) {
   }
   gsx_status fl = upload_factor_lists(c, nullptr);
   if (fl != GSX_OK) return fl;
+  if (c->n_smart) {
+    std::vector<int> slot(P.n_factors, -1), never(c->n_smart, -1);
+    int ns = 0;
+    for (int f = 0; f < P.n_factors; ++f)
+      if (P.f_type[f] == GSX_F_SMART_PROJECTION) slot[f] = ns++;
+    HIPCHK(c, c->d_smart_slot.upload(slot, st));
+    HIPCHK(c, c->d_smart_status.upload(never, st));
+    HIPCHK(c, c->d_smart_counters.alloc(2));
+    HIPCHK(c, c->d_smart_cams.alloc((size_t)ns * 8 * 32));
+    HIPCHK(c, c->d_smart_cache.alloc((size_t)ns * 8 * 12));
+    HIPCHK(c, c->d_smart_point.alloc((size_t)ns * 3));
+    HIPCHK(c, hipMemsetAsync(c->d_smart_counters.p, 0, 2 * sizeof(int), st));
+    HIPCHK(c, hipMemsetAsync(c->d_smart_cache.p, 0, (size_t)ns * 8 * 12 * sizeof(double), st));
+    HIPCHK(c, hipMemsetAsync(c->d_smart_point.p, 0xFF, (size_t)ns * 3 * sizeof(double), st));   // (all-ones bytes are a NaN)
+    c->SD = SmartDev{c->d_smart_slot.p, c->d_smart_cams.p, c->d_smart_cache.p, c->d_smart_point.p, c->d_smart_status.p,
+                     c->d_smart_counters.p, ns};
+  } else {
+    c->SD = SmartDev{};
+  }
   HIPCHK(c, c->d_values.alloc(std::max<int64_t>(P.state_size, 1)));
   HIPCHK(c, c->d_trial.alloc(std::max<int64_t>(P.state_size, 1)));
   HIPCHK(c, c->d_delta.alloc(std::max<int64_t>(P.tan_size, 1)));
@@ -1228,9 +1258,10 @@ void shard_allreduce(gsx_context* c, double* dptr, int64_t n) {
 void dev_linearize(gsx_context* c) {
   timer_begin(c, PH_LINEARIZE);
   hipMemsetAsync(&c->d_status.p->n_cheirality, 0, sizeof(int), c->stream);
+  c->smart_begin(true);
   const int* lists[kNumTypeLists];
   for (int k = 0; k < kNumTypeLists; ++k) lists[k] = c->d_type_list[k].p;
-  launch_linearize(c->DP, lists, c->type_count, c->d_values.p, c->d_jac.p, c->d_status.p, c->stream);
+  launch_linearize(c->DP, lists, c->type_count, c->d_values.p, c->d_jac.p, c->d_status.p, c->stream, &c->SD);
   timer_end(c, PH_LINEARIZE);
   c->sc_dirty |= kXLin;
   c->linearized = true;
@@ -1666,7 +1697,9 @@ void dev_error(gsx_context* c, const double* d_vals, int slot) {
   timer_begin(c, PH_ERROR);
   const int* lists[kNumTypeLists];
   for (int k = 0; k < kNumTypeLists; ++k) lists[k] = c->d_type_list[k].p;
-  launch_error(c->DP, lists, c->type_count, d_vals, c->d_partials.p, gsx_context::kPartials, c->d_scalars.p, slot, c->stream);
+  c->smart_begin(false);
+  launch_error(c->DP, lists, c->type_count, d_vals, c->d_partials.p, gsx_context::kPartials, c->d_scalars.p, slot, c->stream,
+               &c->SD);
   c->sc_dirty |= 1u << slot;
   timer_end(c, PH_ERROR);
 }
@@ -1895,6 +1928,7 @@ gsx_status gsx_create(const gsx_problem_desc* desc, int32_t device, gsx_handle* 
     delete c;
     return st;
   }
+  c->n_smart = (int)std::count(c->P.f_type.begin(), c->P.f_type.end(), (int)GSX_F_SMART_PROJECTION);
   c->device = device;
   {
     const char* e = std::getenv("GSX_FUSED_STAR");
@@ -1963,6 +1997,10 @@ gsx_status gsx_set_ordering(gsx_handle h, const uint64_t* keys, int32_t n) {
       return GSX_E_BAD_ORDERING;
     }
     ord[i] = it->second;
+  }
+  if (h->sharded() && h->n_smart) {
+    h->err = "a sharded handle takes no smart projection factors (their re-triangulation cache is per handle)";
+    return GSX_E_STATE;
   }
   gsx_status st = symbolic_analysis(h->P, ord, h->relax, h->relax_max_f, h->shard_rank, h->shard_world, h->S, h->err);
   if (st != GSX_OK) return st;
@@ -2739,7 +2777,8 @@ gsx_status partial_linearize(gsx_handle h, std::vector<int>& dfac) {
       cnt[k] = (int)lists[k].size();
     }
     timer_begin(h, PH_LINEARIZE);
-    launch_linearize(h->DP, lp, cnt, h->d_values.p, h->d_jac.p, h->d_status.p, sm);
+    h->smart_begin(true);
+    launch_linearize(h->DP, lp, cnt, h->d_values.p, h->d_jac.p, h->d_status.p, sm, &h->SD);
     timer_end(h, PH_LINEARIZE);
   }
   h->lin0_ready = false;   // (some [A b] blocks changed)
@@ -3179,6 +3218,7 @@ static gsx_status gsx_update_impl(gsx_handle h, const gsx_problem_desc* desc, co
   const auto t0 = std::chrono::steady_clock::now();
   h->P = std::move(P2);
   const HostProblem& P = h->P;
+  h->n_smart = (int)std::count(P.f_type.begin(), P.f_type.end(), (int)GSX_F_SMART_PROJECTION);   // (the cache starts empty again)
   st = upload_problem(h);
   if (st != GSX_OK) return st;
   if (std::getenv("GSX_INJECT_UPDATE_FAILURE")) {   // (tests/test_gpu_update.py: a failure in the middle of the switch)
@@ -3846,8 +3886,29 @@ gsx_status gsx_get_stats(gsx_handle h, gsx_stats* out) {
   out->n_cheirality = h->n_cheirality;
   out->n_pcg_iterations = h->pcg_iterations;
   out->n_pcg_solves = h->pcg_solves;
+  if (h->has_device && h->n_smart) {   // (the stream is idle: timers_resolve above waited for it)
+    int cnt[2] = {0, 0};
+    if (hipMemcpy(cnt, h->d_smart_counters.p, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess) {
+      out->n_smart_invalid = cnt[0];
+      out->n_smart_retriangulated = cnt[1];
+    }
+  }
   out->amalgamation_relax = h->S.relax;
   out->amalgamation_max_frontal_dim = h->S.relax_max_f;
+  return GSX_OK;
+}
+
+gsx_status gsx_smart_points(gsx_handle h, double* points_out, int32_t* status_out, int64_t n) {
+  if (!h || n != h->n_smart) return GSX_E_INVALID;
+  if (n == 0) return GSX_OK;
+  gsx_status st = need_device(h);
+  if (st != GSX_OK) return st;
+  hipSetDevice(h->device);
+  if (points_out)
+    HIPCHK(h, hipMemcpyAsync(points_out, h->d_smart_point.p, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (status_out)
+    HIPCHK(h, hipMemcpyAsync(status_out, h->d_smart_status.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return GSX_OK;
 }
 

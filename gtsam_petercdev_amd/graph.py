@@ -1109,6 +1109,115 @@ def triangulateLandmarks(graph, values: "Values", params: Optional[Triangulation
     return out, {int(arr.var_keys[v]): int(s) for v, s in zip(lm, status)}
 
 
+# ---- smart projection factors (gtsam/slam/SmartProjectionPoseFactor.h, SmartProjectionFactor.h, SmartFactorParams.h) ---------
+HESSIAN, IMPLICIT_SCHUR, JACOBIAN_Q, JACOBIAN_SVD = range(4)            # LinearizationMode
+IGNORE_DEGENERACY, ZERO_ON_DEGENERACY, HANDLE_INFINITY = range(3)       # DegeneracyMode
+
+
+class SmartProjectionParams:
+    """SmartProjectionParams (SmartFactorParams.h:40-137) with the reference's defaults: HESSIAN, IGNORE_DEGENERACY,
+    rankTol 1, enableEPI false, retriangulationThreshold 1e-5, no distance and no outlier threshold.  The backend offers no
+    linearization mode (HESSIAN and JACOBIAN_SVD give the same normal equations at lambda = 0) and takes only
+    ZERO_ON_DEGENERACY: a factor with another degeneracy mode raises ValueError when its graph is lowered."""
+
+    def __init__(self, linMode=HESSIAN, degMode=IGNORE_DEGENERACY, throwCheirality=False, verboseCheirality=False,
+                 retriangulationTh=1e-5):
+        self.linearizationMode, self.degeneracyMode = linMode, degMode
+        self.triangulation = TriangulationParameters()   # rankTolerance 1.0, enableEPI false, -1, -1
+        self.retriangulationThreshold = float(retriangulationTh)
+        self.throwCheirality, self.verboseCheirality = throwCheirality, verboseCheirality
+
+    def setLinearizationMode(self, m): self.linearizationMode = m
+    def setDegeneracyMode(self, m): self.degeneracyMode = m
+    def setRankTolerance(self, v): self.triangulation.rankTolerance = float(v)
+    def setEnableEPI(self, v): self.triangulation.enableEPI = bool(v)
+    def setLandmarkDistanceThreshold(self, v): self.triangulation.landmarkDistanceThreshold = float(v)
+    def setDynamicOutlierRejectionThreshold(self, v): self.triangulation.dynamicOutlierRejectionThreshold = float(v)
+    def setRetriangulationThreshold(self, v): self.retriangulationThreshold = float(v)
+    def getLinearizationMode(self): return self.linearizationMode
+    def getDegeneracyMode(self): return self.degeneracyMode
+    def getTriangulationParameters(self): return self.triangulation
+    def getRetriangulationThreshold(self): return self.retriangulationThreshold
+
+
+class SmartProjectionPose3Factor:
+    """SmartProjectionPoseFactor<Cal3_S2>(sharedNoiseModel, K[, body_P_sensor][, params]): one factor per track, lowered to
+    GSX_F_SMART_PROJECTION.  Limits of the backend (include/gsx.h): 2 to 8 views, an Isotropic or Unit model of dimension 2,
+    ZERO_ON_DEGENERACY only."""
+    ftype = A.F_SMART_PROJECTION
+    MAX_VIEWS = 8
+
+    def __init__(self, model, K: "Cal3_S2", body_P_sensor: Optional["Pose3"] = None,
+                 params: Optional[SmartProjectionParams] = None):
+        model = model if model is not None else noiseModel.Unit.Create(2)
+        if model.dim() != 2 or model.kind not in (A.NOISE_UNIT, A.NOISE_ISOTROPIC):
+            raise ValueError("SmartFactorBase: needs isotropic (an Isotropic or Unit model of dimension 2)")
+        self.noise, self.K_ = model, K
+        self.sensor_ = None if body_P_sensor is None else _sensor_state(body_P_sensor, Pose3)
+        self.params_ = params if params is not None else SmartProjectionParams()
+        self.keys_: List[int] = []
+        self.measured_: List[np.ndarray] = []
+        self._result = TriangulationResult(TriangulationResult.DEGENERATE)   # (the reference's default-constructed result_)
+
+    def add(self, measured, key):
+        if int(key) in self.keys_:
+            raise ValueError("SmartFactorBase::add: adding duplicate measurement for key.")
+        self.measured_.append(np.asarray(measured, dtype=float).reshape(2))
+        self.keys_.append(int(key))
+
+    def keys(self): return list(self.keys_)
+    def measured(self): return [m.copy() for m in self.measured_]
+    def size(self): return len(self.keys_)
+
+    @property
+    def rows(self):
+        return 2 * len(self.keys_) - 3
+
+    @property
+    def meas(self):
+        p, t = self.params_, self.params_.triangulation
+        if p.degeneracyMode != ZERO_ON_DEGENERACY:
+            raise ValueError("SmartProjectionPose3Factor: the backend takes only ZERO_ON_DEGENERACY (IGNORE_DEGENERACY and "
+                             "HANDLE_INFINITY need the point at infinity); set params.setDegeneracyMode(ZERO_ON_DEGENERACY)")
+        if not 2 <= len(self.keys_) <= self.MAX_VIEWS:
+            raise ValueError(f"SmartProjectionPose3Factor: {len(self.keys_)} views; the backend takes 2 to {self.MAX_VIEWS}")
+        head = [self.K_.vector(), [t.rankTolerance, float(t.enableEPI), t.landmarkDistanceThreshold,
+                                   t.dynamicOutlierRejectionThreshold, p.retriangulationThreshold, float(p.degeneracyMode)]]
+        if self.sensor_ is not None:
+            head.append(self.sensor_)
+        return np.concatenate(head + self.measured_)
+
+    def point(self) -> "TriangulationResult":
+        """The result of the last triangulation a backend did for this factor (after an optimizer's optimize() / values() /
+        error(), or this factor's own error(values))."""
+        return self._result
+
+    def error(self, values: "Values", backend_factory=None) -> float:
+        g = NonlinearFactorGraph()
+        g.add(self)
+        sub = Values()
+        for k in self.keys_:
+            sub.insert(k, values.at(k))
+        be = _make_backend(g.to_arrays(sub), backend_factory)
+        try:
+            e = be.error()
+            _sync_smart_results(g, be)
+            return e
+        finally:
+            be.close()
+
+
+def _sync_smart_results(graph, backend):
+    """SmartProjectionFactor::point(): copy the handle's last triangulations into the graph's smart factors"""
+    # (an optimizer accepts any object that lowers itself with to_arrays: only a graph with a factor list can hold smart factors)
+    smart = [f for f in getattr(graph, "factors", ()) if f is not None and getattr(f, "ftype", None) == A.F_SMART_PROJECTION]
+    if not smart or not hasattr(backend, "smart_points"):
+        return
+    pts, st = backend.smart_points()
+    for f, p, s in zip(smart, pts, st):
+        f._result = TriangulationResult(s if s >= 0 else TriangulationResult.DEGENERATE, p)
+
+
 def _make_backend(arrays, backend_factory):
     if backend_factory is None:
         from ._lib import product_backend
@@ -1230,11 +1339,14 @@ class _OptimizerBase:
         self.result = None
 
     def values(self) -> Values:
+        _sync_smart_results(self.graph_, self.backend)
         return Values.unpack(self.arrays.var_keys, self.arrays.var_types, self.arrays.var_dims,
                              self.backend.get_values())
 
     def error(self) -> float:
-        return self.backend.error()
+        e = self.backend.error()
+        _sync_smart_results(self.graph_, self.backend)
+        return e
 
     def iterations(self) -> int:
         return self.result["iterations"] if self.result else self._iterations

@@ -156,7 +156,7 @@ enum {
                                gives zero Jacobians and the constant error
                                (2 fx, 2 fx, 2 fx); the sensor form counts it in
                                n_cheirality                                        */
-  GSX_F_SFM2 = 9            /* GeneralSFMFactor2<Cal3_S2> (gtsam/slam/
+  GSX_F_SFM2 = 9,           /* GeneralSFMFactor2<Cal3_S2> (gtsam/slam/
                                GeneralSFMFactor.h:208-278): the calibration is a
                                variable.  Keys (POSE3, VECTOR(3), VECTOR(5)), the
                                last one Cal3_S2 as (fx, fy, s, u0, v0) — it retracts
@@ -166,6 +166,27 @@ enum {
                                (Cal3_S2.cpp:54-62).  Cheirality (:270-277): zero
                                Jacobians and a ZERO error — not the 2 fx of
                                GSX_F_PROJECTION — counted in n_cheirality          */
+  GSX_F_SMART_PROJECTION = 10 /* SmartProjectionPoseFactor<Cal3_S2> (gtsam/slam/SmartProjectionPoseFactor.h,
+                               SmartProjectionFactor.h, SmartFactorBase.h): one factor per track.  At every
+                               linearization it triangulates the landmark from the current poses (triangulateSafe, DLT,
+                               no noise model; the LM refinement with enable_epi), marginalizes it and hands the
+                               optimizer a factor on the poses alone.  See "Smart projection factors" below.
+                               Keys: nk POSE3 variables, 2 <= nk <= 8 — a LIMIT: 8 is the key limit of the assembly
+                               (GSX_F_LINEAR's), and the reference returns a zero factor for a single view where this
+                               library returns GSX_E_INVALID.  Rows: m = 2 nk - 3, those of the reference's
+                               JacobianFactorSVD.  Noise: GSX_NOISE_ISOTROPIC (one sigma) or GSX_NOISE_UNIT only
+                               (SmartFactorBase throws "needs isotropic" otherwise); no robust bit.
+                               meas = (fx, fy, s, u0, v0,
+                                       rank_tol, enable_epi, landmark_distance_threshold,
+                                       dynamic_outlier_rejection_threshold   [SmartProjectionParams::triangulation],
+                                       retriangulation_threshold, degeneracy_mode),
+                               optionally body_P_sensor as a Pose3 state (12 doubles; told by the length, as with
+                               GSX_F_PROJECTION), then 2 nk pixel coordinates in key order.
+                               degeneracy_mode: only ZERO_ON_DEGENERACY (1) is taken; IGNORE_DEGENERACY (0) and
+                               HANDLE_INFINITY (2) go through backprojectPointAtInfinity and a Unit3 tangent basis and
+                               return GSX_E_INVALID — the reference's SmartProjectionRigFactor makes the same restriction.
+                               No linearization mode is offered: HESSIAN and JACOBIAN_SVD give the same normal equations
+                               at lambda = 0, which is what NonlinearFactorGraph::linearize passes                   */
 };
 
 /* ---- noise model kinds (gtsam/linear/NoiseModel.cpp) --------------------- */
@@ -312,6 +333,8 @@ typedef struct gsx_stats {
   int64_t n_constrained_fronts;  /* fronts that take constraint rows in (always blocked; constraint pivots before Cholesky) */
   int64_t n_pcg_iterations;      /* PCG iterations since the last gsx_reset_stats (gsx_solve_pcg and the drivers of a PCG handle) */
   int64_t n_pcg_solves;          /* ... and the solves they belong to */
+  int64_t n_smart_invalid;       /* smart factors whose last linearize found no valid point (an all-zero block) */
+  int64_t n_smart_retriangulated;/* smart factors the last linearize or error evaluation actually re-triangulated */
 } gsx_stats;
 
 /* ---- on-disk formats (host only) -------------------------
@@ -893,6 +916,30 @@ gsx_status gsx_triangulate_landmarks(const gsx_problem_desc* desc, const double*
  * [0] host: sorting the tracks into the two classes; [1] triangulate_cameras_kernel; [2] triangulate_short_kernel; [3]
  * triangulate_long_kernel; [4] the whole call on the host clock, transfers included.  [1]-[3] are HIP events. */
 gsx_status gsx_triangulate_timings(double* out_ms, int32_t n);
+
+/* ---- Smart projection factors (GSX_F_SMART_PROJECTION) ------------------------------------------------------------------------
+ * Linearization (csrc/smart_math.h, csrc/smart.hip): with a VALID point, per view F_i (2 x 6: PinholePose's projection
+ * Jacobian with respect to the pose, times the compose Jacobian of SmartFactorBase.h:225-236 with body_P_sensor), E_i (2 x 3)
+ * and b_i = z_i - h_i, all whitened by 1 / sigma; then three Householder reflectors of E (2 nk x 3) are applied to [F b] and
+ * rows 3 .. 2 nk - 1 are the factor's block A = Q_2'[F b].  Any orthonormal basis Q_2 of the left null space of E gives the
+ * reference's F'F - F'E (E'E)^-1 E'F with its gradient and constant term, so the block is comparable with the reference
+ * through [A b]'[A b] only, never entry by entry.  Without a valid point: the all-zero block and the error 0
+ * (SmartProjectionFactor.h:214-220, :427-429).  The error is totalReprojectionError: 0.5 |whitened (h - z)|^2 over all 2 nk
+ * rows at the triangulated point — not 0.5 |b|^2 of the projected block; the two differ in the reference as well.
+ * The re-triangulation cache (decideIfTriangulate, SmartProjectionFactor.h:127-165) lives in the handle, per factor: the
+ * camera poses of the last triangulation, its point and its status.  It is empty after gsx_create and after gsx_update.
+ * Every call that evaluates a smart factor consults and updates it in stream order — gsx_linearize, gsx_error, the trial
+ * error of gsx_retract, gsx_lm_trial, the drivers, gsx_relinearize_partial — and re-triangulates only when some camera pose
+ * differs from the cached one by more than retriangulation_threshold in an entry of R or t (Pose3::equals).  With a
+ * threshold of 0 only bit-identical poses reuse the cached point, which is the point a new triangulation would give.
+ * Limit: a cached point that is no longer in front of every camera at the current poses (the reference throws
+ * CheiralityException there) gives the all-zero block / the error 0, counted in n_smart_invalid.
+ * A sharded handle with a smart factor in its graph: GSX_E_STATE from gsx_set_ordering.
+ * gsx_smart_points: SmartProjectionFactor::point() of every smart factor in graph order — the point of its last
+ * triangulation (NaN unless VALID) in points_out [3 n] and its GSX_TRI_* status, or -1 when it was never triangulated, in
+ * status_out [n]; either array may be NULL.  n must be the number of smart factors of the graph (GSX_E_INVALID otherwise;
+ * n = 0 with no smart factor is GSX_OK). */
+gsx_status gsx_smart_points(gsx_handle h, double* points_out, int32_t* status_out, int64_t n);
 
 /* ---- dense kernel exposed for unit parity (gtsam/base/cholesky.cpp:108-159) -- */
 /* In-place partial Cholesky of an n x n column-major symmetric matrix (upper
