@@ -110,15 +110,15 @@ class LinearSystem:
         d = np.clip(np.diag(self.H), LD(min_diagonal), LD(max_diagonal)) if diag else np.ones(self.n, LD)
         return LD(lam) * d
 
-    def damped(self, lam, diag):
+    def damped(self, lam, diag, limits=(1e-6, 1e32)):
         Hd = self.H.copy()
-        Hd[np.diag_indices(self.n)] += self.damping(lam, diag)
+        Hd[np.diag_indices(self.n)] += self.damping(lam, diag, *limits)
         return Hd
 
-    def times(self, x, lam=0.0, diag=False):
+    def times(self, x, lam=0.0, diag=False, limits=(1e-6, 1e32)):
         """Hd x from the factor blocks."""
         x = np.asarray(x, LD)
-        y = self.damping(lam, diag) * x
+        y = self.damping(lam, diag, *limits) * x
         for idx, A, _ in self.blocks:
             y[idx] += np.dot(A.T, np.dot(A, x[idx]))
         return y
@@ -188,14 +188,14 @@ def _ratio(lhs, rhs):
     return float(np.max(lhs[pos] / rhs[pos]) / LD(U)) if pos.any() else 0.0
 
 
-def factor_ratio(system, F, lam, diag):
+def factor_ratio(system, F, lam, diag, limits=(1e-6, 1e32)):
     """Measure (1) in units of u; infinite when a structural zero is not zero: an entry of R below the diagonal (in
     elimination order), or a difference where the bound is exactly 0."""
     if np.any(np.tril(F.R[np.ix_(F.order, F.order)], -1) != 0):
         return float("inf")
     bound = F.aRtaR + system.absH
-    bound[np.diag_indices(system.n)] += system.damping(lam, diag)
-    return _ratio(F.RtR - system.damped(lam, diag), bound)
+    bound[np.diag_indices(system.n)] += system.damping(lam, diag, *limits)
+    return _ratio(F.RtR - system.damped(lam, diag, limits), bound)
 
 
 def rhs_ratio(system, F):
@@ -203,11 +203,11 @@ def rhs_ratio(system, F):
     return _ratio(np.dot(F.R.T, F.d) - system.g, np.dot(np.abs(F.R).T, np.abs(F.d)) + system.absg)
 
 
-def solve_ratio(system, F, x, lam, diag):
+def solve_ratio(system, F, x, lam, diag, limits=(1e-6, 1e32)):
     """Measure (3) in units of u."""
     ax = np.abs(np.asarray(x, LD))
-    bound = np.dot(F.aRtaR, ax) + np.dot(system.absH, ax) + system.damping(lam, diag) * ax + system.absg
-    return _ratio(system.times(x, lam, diag) - system.g, bound)
+    bound = np.dot(F.aRtaR, ax) + np.dot(system.absH, ax) + system.damping(lam, diag, *limits) * ax + system.absg
+    return _ratio(system.times(x, lam, diag, limits) - system.g, bound)
 
 
 def _converged(rel, prev, kappa, what):
@@ -297,13 +297,15 @@ class Judge:
         self._star = {}
         self._sigma = None
 
-    def backward(self, backend, x, lam, diag):
-        """(factor, rhs, solve) ratios in u for the backend's conditionals, taken as the factorization at (lam, diag)."""
+    def backward(self, backend, x, lam, diag, limits=(1e-6, 1e32)):
+        """(factor, rhs, solve) ratios in u for the backend's conditionals, taken as the factorization at (lam, diag);
+        limits = (min_diagonal, max_diagonal) of the diagonal damping's clamp."""
         F = gather(backend, self.sys)
-        return factor_ratio(self.sys, F, lam, diag), rhs_ratio(self.sys, F), solve_ratio(self.sys, F, x, lam, diag)
+        return (factor_ratio(self.sys, F, lam, diag, limits), rhs_ratio(self.sys, F),
+                solve_ratio(self.sys, F, x, lam, diag, limits))
 
-    def check_backward(self, backend, x, lam, diag, what):
-        f, r, s = self.backward(backend, x, lam, diag)
+    def check_backward(self, backend, x, lam, diag, what, limits=(1e-6, 1e32)):
+        f, r, s = self.backward(backend, x, lam, diag, limits)
         print(f"{what} lam={lam:g} diag={int(diag)} n={self.sys.n} m={self.sys.m}: factor {f:.2f}u (k {self.kf}), "
               f"rhs {r:.2f}u (k {self.kf}), solve {s:.2f}u (k {self.ks})")
         assert f <= self.kf, (what, "factor", lam, diag, f, self.kf)

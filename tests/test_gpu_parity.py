@@ -713,6 +713,7 @@ def test_planar_slam_parity(gpu, oracle, robust):
 
 def test_lm_trial_equals_separate_calls(gpu):
     """gsx_lm_trial = linearize + damped solve + both linearized errors + retract + trial error in one call."""
+    # (the derived float64 bound on e(0) and on the model decrease is in test_gpu_scalar_bounds.py::test_model_path)
     arr = PROBLEMS["pose3"]
     a, b = gpu.product_backend(arr), gpu.product_backend(arr)
     ordering = a.compute_ordering(A.ORDER_ND)
