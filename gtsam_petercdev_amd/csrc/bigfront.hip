@@ -8,7 +8,7 @@
 //                 whole factorization, as 16 x 16 tiles in the matrix-core accumulator layout spread over the
 //                 workgroup's waves; only the four current columns pass through LDS (two LDS barriers per four
 //                 pivots).  This is the only sequential chain of a front: F pivots.
-//   B. big_rows   L21 = A21 L11^-T               one workgroup per 32 rows of A21 (and the rhs row): blocked forward
+//   B. big_rows   L21 = A21 L11^-T               one workgroup per 32 or 64 rows of A21 (and the rhs row): blocked forward
 //                 substitution along the row block, every product on the matrix cores, no inter-workgroup
 //                 dependency at all — the rows of L21 are independent of each other once L11 is known.
 //   C. big_schur  A22 -= L21 L21'                one workgroup per lower 32 x 32 tile pair, operands streamed straight
@@ -642,12 +642,12 @@ __global__ void __launch_bounds__(NW * 64) big_diag_rows_kernel(const BigDesc* d
   }
 }
 
-// lane roles of the 256-thread kernels: wave wv owns the 16 x 16 quadrant (row half wv & 1, column half wv >> 1) of
-// a 32 x 32 tile; entry q of a lane = (row r0 + li, column cq0 + 4 q + lk)
+// lane roles of the matrix-core kernels below: a group of four waves shares a 32 x 32 tile, wave wv owns the 16 x 16
+// quadrant (row half wv & 1, column half (wv >> 1) & 1); entry q of a lane = (row r0 + li, column cq0 + 4 q + lk)
 struct Quad {
   int li, lk, r0, cq0;
   __device__ __forceinline__ Quad() {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wv = (threadIdx.x >> 6) & 3;
     li = lane & 15;
     lk = lane >> 4;
     r0 = 16 * (wv & 1);
@@ -655,44 +655,54 @@ struct Quad {
   }
 };
 
-// ---- B. rows of L21 (and the rhs row): X_i = A_i L11^-T, 32 rows per workgroup --------------------------------------
+// ---- B. rows of L21 (and the rhs row): X_i = A_i L11^-T, 32 NH rows per workgroup -----------------------------------
 // Right-looking along the row block:  X_ik = T_k (L_kk^-1)'  then  T_k' -= X_ik L_k'k'  for every k' > k.
 // The 32 x 32 tiles T_k of the row block stay in matrix-core accumulators; the tiles of L11's column block k (the
 // diagonal tile's inverse left by big_diag and the L tiles below it) are staged through LDS, double-buffered: the
 // loads of column block k+1 are in flight during step k.  The dependent chain of a step is LDS -> 8 products -> LDS ->
 // 8 products; nothing on it touches global memory.
+// NH = 2: eight waves, two row halves of 32 rows (waves 0-3 the first, waves 4-7 the second), each with its own T / X
+// tile in LDS and its own accumulators, both reading the SAME staged column blocks of L11: L11 crosses the memory
+// system once per 64 rows, and the second half's products fill the matrix cores while the first half waits on LDS.
+// A half past the front's last row runs on zeros and stores nothing.  Every entry of X is the same sequence of
+// matrix-core instructions, in the same k / s order, whichever form computes it.
 static_assert(kMaxChunk / T == 6, "launch_big_rows dispatches on 1..6 column steps");
 constexpr int TS = T * (T + 2);       // an LDS tile: row stride 34 doubles (operand reads conflict-free)
+constexpr size_t kLdsPerCU = 160 * 1024;
 
 // NK = 32-column steps of the widest chunk of the launch group (a narrower chunk runs its missing steps on tiles of
 // zeros: no run-time guards, the whole kernel is straight-line code over register arrays)
-template <int NK>
-__global__ void __launch_bounds__(256) big_rows_kernel(const BigDesc* descs, int c0, int chunk, double* arena) {
+template <int NK, int NH>
+__global__ void __launch_bounds__(256 * NH) big_rows_kernel(const BigDesc* descs, int c0, int chunk, double* arena) {
   extern __shared__ double dyn[];
+  constexpr int RB = T * NH;          // rows of a workgroup's row block
+  constexpr int NQ = 4 / NH;          // elements of a staged tile a thread carries
+  constexpr int EH = 8 * NH;          // ... at slow indices ehi + EH q
   const BigDesc d = descs[blockIdx.y];
   const int n = d.N, F = d.F;
   if (c0 >= F) return;
   const int fw = min(chunk, F - c0), base = c0 + fw;
-  const int nrb = (n - base + T - 1) / T;
+  const int nrb = (n - base + RB - 1) / RB;
   if ((int)blockIdx.x >= nrb) return;
   constexpr int nk = NK;
+  const int tid = threadIdx.x;
+  const int half = __builtin_amdgcn_readfirstlane(tid >> 8);
   double* Lb = dyn;                                   // [2][nk] tiles: column block k = inverse of L_kk, then L_k'k, k' > k
-  double(*Tt)[T + 2] = (double(*)[T + 2])(dyn + (size_t)2 * nk * TS);
-  double(*Xt)[T + 2] = (double(*)[T + 2])(dyn + (size_t)(2 * nk + 1) * TS);
+  double(*Tt)[T + 2] = (double(*)[T + 2])(dyn + (size_t)(2 * nk + 2 * half) * TS);   // (one T / X pair per row half)
+  double(*Xt)[T + 2] = (double(*)[T + 2])(dyn + (size_t)(2 * nk + 2 * half + 1) * TS);
   double* A = arena + d.off;
   double* X = arena + d.xoff;
   const Quad L;
-  const int tid = threadIdx.x, row = L.r0 + L.li;
-  // element e = tid + 256 q of a tile as (lo = e & 31, hi = e >> 5): the fast index of the global read
+  const int row = L.r0 + L.li;        // row inside this half's 32-row tile
+  // element e = tid + 256 NH q of a tile as (lo = e & 31, hi = e >> 5): the fast index of the global read
   const int elo = tid & 31, ehi = tid >> 5;
 
-  // column block kc of L11 into registers (4 doubles a thread per tile) / from registers into LDS buffer kc & 1
-  double stg[NK][4];
-  auto fetch = [&](int kc) {
+  // column block kc of L11 into registers (NQ doubles a thread per tile) / from registers into LDS buffer kc & 1
+  auto fetch = [&](int kc, double (&stg)[NK][NQ]) {
     const int ck = c0 + kc * T, wk = min(T, fw - kc * T);  // (wk <= 0 beyond a narrower chunk: tiles of zeros)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {  // tile 0: (L_kk^-1)[c][kk], kk <= c — strictly upper triangle of the diagonal tile
-      const int kk = elo, c = ehi + 8 * q;  //   (transposed), 1 / L_cc on the L-panel area's diagonal
+    for (int q = 0; q < NQ; ++q) {  // tile 0: (L_kk^-1)[c][kk], kk <= c — strictly upper triangle of the diagonal tile
+      const int kk = elo, c = ehi + EH * q;  //   (transposed), 1 / L_cc on the L-panel area's diagonal
       double v = 0.0;
       if (c < wk && kk < c) v = A[(ck + kk) + (i64)(ck + c) * n];
       else if (c < wk && kk == c) v = X[(ck + c) + (i64)(ck + c) * n];
@@ -703,29 +713,39 @@ __global__ void __launch_bounds__(256) big_rows_kernel(const BigDesc* descs, int
       if (kc + t < nk) {
         const int rr = (kc + t) * T;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int c = elo, kk = ehi + 8 * q;
+        for (int q = 0; q < NQ; ++q) {
+          const int c = elo, kk = ehi + EH * q;
           stg[t][q] = (rr + c < fw && kk < wk) ? X[(c0 + rr + c) + (i64)(ck + kk) * n] : 0.0;
         }
       }
     }
   };
-  auto stash = [&](int kc) {
+  auto stash = [&](int kc, const double (&stg)[NK][NQ]) {
     double* buf = Lb + (size_t)(kc & 1) * nk * TS;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) buf[(ehi + 8 * q) * (T + 2) + elo] = stg[0][q];  // [c][kk]
+    for (int q = 0; q < NQ; ++q) buf[(ehi + EH * q) * (T + 2) + elo] = stg[0][q];  // [c][kk]
 #pragma unroll
     for (int t = 1; t < NK; ++t) {
       if (kc + t < nk) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) buf[(size_t)t * TS + elo * (T + 2) + ehi + 8 * q] = stg[t][q];  // [c][kk]
+        for (int q = 0; q < NQ; ++q) buf[(size_t)t * TS + elo * (T + 2) + ehi + EH * q] = stg[t][q];  // [c][kk]
       }
     }
   };
 
+  // The 64-row form (the only one whose grid the launcher caps, so the only one that strides over several row blocks)
+  // fetches column block 0 from global memory ONCE per workgroup and keeps it in registers: it is the block whose
+  // fetch no product hides.  Blocks 1 .. NK-1 are fetched again for every row block, behind the products of the step
+  // before.  Keeping them too would take either all NK (NK + 1) / 2 tiles of L11 in LDS (183 KB at six steps, with
+  // 136 KB in use of a CU's 160) or the accumulators of every row block of a pass in registers (48 a row block, in a
+  // kernel that stands at 245 of 256): neither fits (an argument from sizes: no launch of the benchmark workloads strides in this form, and nothing
+  // was measured).  The 32-row form fetches block 0 per row block as it always
+  // did: its grid is never capped, and its five- and six-step instances already fill the register file.
+  double stg0[NK][NQ], stg[NK][NQ];   // (stg0: the 64-row form only)
+  if constexpr (NH == 2) fetch(0, stg0);
   for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
-    const int ri = base + T * rb, hi = min(T, n - ri);
-    fetch(0);
+    const int ri = base + RB * rb + T * half, hi = min(T, n - ri);  // (hi <= 0: the second half of the last row block is empty)
+    if constexpr (NH == 1) fetch(0, stg);
     v4d tk[NK];
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
@@ -737,12 +757,13 @@ __global__ void __launch_bounds__(256) big_rows_kernel(const BigDesc* descs, int
       }
     }
     lds_bar();  // (a previous row block's reads of the buffers are done)
-    stash(0);
+    if constexpr (NH == 2) stash(0, stg0);
+    else stash(0, stg);
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
       const int wk = min(T, fw - k * T);
       const double* buf = Lb + (size_t)(k & 1) * nk * TS;
-      if (k + 1 < nk) fetch(k + 1);
+      if (k + 1 < nk) fetch(k + 1, stg);
 #pragma unroll
       for (int q = 0; q < 4; ++q) Tt[row][L.cq0 + 4 * q + L.lk] = tk[k][q];
       lds_bar();
@@ -768,7 +789,7 @@ __global__ void __launch_bounds__(256) big_rows_kernel(const BigDesc* descs, int
         for (int s = 0; s < 8; ++s)
           tk[k2] = __builtin_amdgcn_mfma_f64_16x16x4f64(-pa[4 * s], Xt[row][4 * s + L.lk], tk[k2], 0, 0, 0);
       }
-      if (k + 1 < nk) stash(k + 1);
+      if (k + 1 < nk) stash(k + 1, stg);
     }
   }
 }
@@ -914,31 +935,86 @@ void launch_big_diag(const BigDesc* descs, int count, const BigPlan& plan, int r
   else big_diag_kernel<12, 7><<<count, 768, lds, st>>>(descs, c0, plan.chunk, arena, status);
 }
 
-template <int NK>
-static void launch_rows_nk(const BigDesc* descs, int count, int gx, int c0, int chunk, double* arena, hipStream_t st) {
-  static bool attr = false;
-  constexpr size_t lds = (size_t)(2 * NK + 2) * TS * sizeof(double);
-  if (!attr) {
-    hipFuncSetAttribute((const void*)big_rows_kernel<NK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  big_rows_kernel<NK><<<dim3(gx, count), 256, lds, st>>>(descs, c0, chunk, arena);
+// The form of big_rows_kernel a launch runs in, and the dynamic LDS it asks for: a chunk of fw frontal columns over
+// `tiles` 32-row blocks in all, on a device of `cus` compute units.  *rows (may be null) = 32 or 64 rows per workgroup;
+// 0 = refused (no such chunk: wider than a round's, or past a CU's LDS).
+// 64 rows when the 32-row grid would be more workgroups than the device has CUs: then L11 crosses the memory system
+// half as often and the launch takes half as many rounds of workgroups.  A launch that fits the device at once keeps
+// 32 rows: nothing is fetched twice for want of room, and a step's two barriers over eight waves cost more than over
+// four.  Both measured with tools/bigfront_bench at every chunk width: profiles/r05_big_rows_forms.txt.
+// `tiles` is the launcher's grid in 32-row blocks, fronts times the TALLEST front's blocks: in a group of unequal
+// heights it counts workgroups that exit at once, so such a group takes the 64-row form somewhat earlier than its real
+// work would; the rule errs towards the form that is cheaper when the device is oversubscribed.
+size_t big_rows_lds(int fw, long tiles, int cus, int* rows) {
+  if (fw <= 0 || fw > kMaxChunk || tiles <= 0 || cus <= 0) return 0;
+  const int nk = (fw + T - 1) / T, nh = tiles > cus ? 2 : 1;
+  const size_t bytes = (size_t)(2 * nk + 2 * nh) * TS * sizeof(double);
+  if (bytes > kLdsPerCU) return 0;  // (the kernel has no static LDS)
+  if (rows) *rows = T * nh;
+  return bytes;
+}
+// (for tests/test_gpu_blocked_rows.py: the sizing above, host only; not part of the C ABI of include/gsx.h)
+extern "C" long long gsxtest_big_rows_lds(int fw, long long tiles, int cus, int* rows) {
+  int r = 0;
+  const size_t bytes = big_rows_lds(fw, (long)tiles, cus, &r);
+  if (rows) *rows = bytes ? r : 0;
+  return (long long)bytes;
 }
 
-void launch_big_rows(const BigDesc* descs, int count, const BigPlan& plan, int round, double* arena, hipStream_t st) {
+namespace {
+__global__ void rows_refused_kernel(const BigDesc* descs, DevStatus* status) { report_failure(status, descs[0].front); }
+
+template <int NK, int NH>
+void launch_rows_nk(const BigDesc* descs, int count, int gx, int c0, int chunk, size_t lds, double* arena, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)big_rows_kernel<NK, NH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr = true;
+  }
+  big_rows_kernel<NK, NH><<<dim3(gx, count), 256 * NH, lds, st>>>(descs, c0, chunk, arena);
+}
+template <int NK>
+void launch_rows(int rows, const BigDesc* descs, int count, int gx, int c0, int chunk, size_t lds, double* arena,
+                 hipStream_t st) {
+  if (rows == 2 * T) launch_rows_nk<NK, 2>(descs, count, gx, c0, chunk, lds, arena, st);
+  else launch_rows_nk<NK, 1>(descs, count, gx, c0, chunk, lds, arena, st);
+}
+}  // namespace
+
+void launch_big_rows(const BigDesc* descs, int count, const BigPlan& plan, int round, double* arena, DevStatus* status,
+                     hipStream_t st) {
   if (!count || plan.rb[round] <= 0) return;
-  // one workgroup per 32-row block; with many fronts in the group a workgroup takes several row blocks of its front in
-  // turn (the column blocks of L11 fill most of the LDS: about one workgroup per CU)
-  int gx = plan.rb[round];
+  static int cus = 0;   // compute units of the device (one device per process: solver.hip)
+  if (!cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      cus = 0;   // (refused below)
+  }
+  int rows = T;
+  const size_t lds = big_rows_lds(plan.fw[round], (long)plan.rb[round] * count, cus, &rows);
+  if (!lds) {  // never with the chunks plan_big_group makes; a launch past the CU's LDS must not reach the GPU
+    fprintf(stderr, "gsx: big_rows cannot stage a chunk of %d columns in LDS (%d CUs): launch refused, the factorization fails\n",
+            plan.fw[round], cus);
+    rows_refused_kernel<<<1, 1, 0, st>>>(descs, status);
+    return;
+  }
+  // one workgroup per row block (plan.rb counts 32-row tiles: big_schur's unit).  With many fronts in the group a
+  // workgroup takes several row blocks of its front in turn.  The cap rests on residency: a workgroup's LDS (the column
+  // blocks of L11 double-buffered, 70-136 KB from three column steps on) admits one or two workgroups per CU, 256-512 on
+  // the device, so 1024 is two to four full rounds of workgroups: enough to even out fronts of unequal height.  A
+  // workgroup past the cap would cost a start and its own fetch of L11's first column block; a workgroup that strides
+  // keeps that block in registers.
+  int gx = (plan.rb[round] * T + rows - 1) / rows;
   if ((long)gx * count > 1024) gx = std::max(1, std::min(gx, 1024 / count));
   const int c0 = round * plan.chunk;
   switch ((plan.fw[round] + T - 1) / T) {
-    case 1: launch_rows_nk<1>(descs, count, gx, c0, plan.chunk, arena, st); break;
-    case 2: launch_rows_nk<2>(descs, count, gx, c0, plan.chunk, arena, st); break;
-    case 3: launch_rows_nk<3>(descs, count, gx, c0, plan.chunk, arena, st); break;
-    case 4: launch_rows_nk<4>(descs, count, gx, c0, plan.chunk, arena, st); break;
-    case 5: launch_rows_nk<5>(descs, count, gx, c0, plan.chunk, arena, st); break;
-    default: launch_rows_nk<6>(descs, count, gx, c0, plan.chunk, arena, st); break;
+    case 1: launch_rows<1>(rows, descs, count, gx, c0, plan.chunk, lds, arena, st); break;
+    case 2: launch_rows<2>(rows, descs, count, gx, c0, plan.chunk, lds, arena, st); break;
+    case 3: launch_rows<3>(rows, descs, count, gx, c0, plan.chunk, lds, arena, st); break;
+    case 4: launch_rows<4>(rows, descs, count, gx, c0, plan.chunk, lds, arena, st); break;
+    case 5: launch_rows<5>(rows, descs, count, gx, c0, plan.chunk, lds, arena, st); break;
+    default: launch_rows<6>(rows, descs, count, gx, c0, plan.chunk, lds, arena, st); break;
   }
 }
 
@@ -1457,6 +1533,11 @@ size_t backsolve_big_lds(int max_n, int max_F, int max_sep_rows) {
   const size_t doubles = (((size_t)max_n + 1) & ~(size_t)1) + nk * T + T + nk * (T * (T + 1) / 2) + nk * (nk - 1) / 2 * T * T;
   const size_t bytes = doubles * sizeof(double);
   return bytes <= 160 * 1024 - 256 ? bytes : 0;
+}
+
+// (for tests/test_gpu_blocked_rows.py: the sizing above, host only; not part of the C ABI of include/gsx.h)
+extern "C" long long gsxtest_backsolve_big_lds(int max_n, int max_F, int max_sep_rows) {
+  return (long long)backsolve_big_lds(max_n, max_F, max_sep_rows);
 }
 
 void launch_backsolve_big(const DevSymbolic& S, const int* ids, int count, int max_n, int max_F, const double* arena,

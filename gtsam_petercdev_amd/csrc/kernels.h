@@ -276,7 +276,12 @@ void launch_big_diag(const BigDesc* descs, int count, const BigPlan& plan, int r
 #ifdef GSX_STAMP
 void big_stamp_dump(const char* what);
 #endif
-void launch_big_rows(const BigDesc* descs, int count, const BigPlan& plan, int round, double* arena, hipStream_t st);
+// rows of L21 below a round's chunk; big_rows_lds = the dynamic LDS its kernel asks for at a chunk of fw columns over
+// `tiles` 32-row blocks in the whole launch on a device of `cus` compute units, and the rows one workgroup takes (*rows,
+// may be null), 0: refused — the launcher then fails the factorization through status
+size_t big_rows_lds(int fw, long tiles, int cus, int* rows);
+void launch_big_rows(const BigDesc* descs, int count, const BigPlan& plan, int round, double* arena, DevStatus* status,
+                     hipStream_t st);
 void launch_big_schur(const BigDesc* descs, int count, const BigPlan& plan, int round, double* arena, hipStream_t st);
 void launch_front_leaf(const DevProblem& P, const DevSymbolic& S, const LeafRec* recs, int count, int max_panel, int threads,
                        const double* H, const double* damp, const double* scalars, double* arena, DevStatus* status,

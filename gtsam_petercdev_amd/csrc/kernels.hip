@@ -3768,7 +3768,7 @@ void launch_dense_partial(double* a, int n, int nf, DevStatus* status, hipStream
   plan_big_group(&h, 1, plan);
   for (int r = 0; r < plan.rounds(); ++r) {
     launch_big_diag(d, 1, plan, r, a, status, st);
-    launch_big_rows(d, 1, plan, r, a, st);
+    launch_big_rows(d, 1, plan, r, a, status, st);
     launch_big_schur(d, 1, plan, r, a, st);
   }
   big_copy_panel_kernel<<<64, 256, 0, st>>>(d, a);

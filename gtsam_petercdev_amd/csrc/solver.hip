@@ -1359,7 +1359,7 @@ void dev_big_factor(gsx_context* c, const BigDesc* descs, int count, const BigPl
     launch_big_diag(descs, count, plan, r, c->d_arena.p, c->d_status.p, st);
     if (prof) timer_end(c, PH_K_POTRF0);
     if (prof) timer_begin(c, PH_K_TRSM);
-    launch_big_rows(descs, count, plan, r, c->d_arena.p, st);
+    launch_big_rows(descs, count, plan, r, c->d_arena.p, c->d_status.p, st);
     if (prof) timer_end(c, PH_K_TRSM);
     if (prof) timer_begin(c, PH_K_SYRK);
     launch_big_schur(descs, count, plan, r, c->d_arena.p, st);

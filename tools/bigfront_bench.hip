@@ -39,7 +39,7 @@ int main(int argc, char** argv) {
       for (int ph = 0; ph < 3; ++ph) {
         hipEventRecord(e0, 0);
         if (ph == 0) launch_big_diag(d, count, plan, r, arena, st, 0);
-        if (ph == 1) launch_big_rows(d, count, plan, r, arena, 0);
+        if (ph == 1) launch_big_rows(d, count, plan, r, arena, st, 0);
         if (ph == 2) launch_big_schur(d, count, plan, r, arena, 0);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
