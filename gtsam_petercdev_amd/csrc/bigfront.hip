@@ -984,7 +984,7 @@ void launch_rows(int rows, const BigDesc* descs, int count, int gx, int c0, int 
 void launch_big_rows(const BigDesc* descs, int count, const BigPlan& plan, int round, double* arena, DevStatus* status,
                      hipStream_t st) {
   if (!count || plan.rb[round] <= 0) return;
-  static int cus = 0;   // compute units of the device (one device per process: solver.hip)
+  static int cus = 0;   // compute units of the device (one device per process: gsx_create)
   if (!cus) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess ||

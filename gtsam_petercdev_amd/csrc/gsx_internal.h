@@ -255,7 +255,7 @@ void lower_lago_poses(const gsx_problem_desc* d, const LagoGraph& G, OwnedDesc& 
 // depth of every node of a forest given by parent links (root: parent[i] == i); false: an index out of range or a cycle
 bool forest_depths(const int32_t* parent, int64_t n, std::vector<int>& depth, int* max_depth);
 
-// seams of initialize.hip into a handle (solver.hip); the pointers are device memory on the handle's device
+// seams of initialize.hip and lago.hip into a handle (solver.hip; the handle itself is handle.h); the pointers are device memory on the handle's device
 double* handle_jacobian_pool(gsx_context* h);   // the [A b] blocks, factor f at HostProblem::f_jac_off[f]
 double* handle_values(gsx_context* h);          // packed Values
 double* handle_delta(gsx_context* h);           // the solution of the last solve, tangent order

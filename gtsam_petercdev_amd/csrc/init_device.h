@@ -13,7 +13,7 @@ namespace initdev {
 
 constexpr int kThreads = 256;
 
-// a failed allocation is GSX_E_NOMEM, every other HIP failure GSX_E_NO_DEVICE (as HIPCHK of solver.hip; there is no
+// a failed allocation is GSX_E_NOMEM, every other HIP failure GSX_E_NO_DEVICE (as HIPCHK of handle.h; there is no
 // handle here to carry an error text)
 #define HIPTRY(expr)                                                            \
   do {                                                                          \

@@ -53,7 +53,7 @@ struct LeafRec {
   int fvar_ptr, front, pad0, pad1;
 };
 // A STAR LEAF (front_star_leaf_kernel): a lean, childless clique whose one frontal variable is of the star group of the
-// H assembly (every BAL landmark, solver.hip: upload_symbolic).  Its factor blocks are read straight from [A b] through
+// H assembly (every BAL landmark, upload.hip: upload_symbolic).  Its factor blocks are read straight from [A b] through
 // the variable's term records (three per factor: own block, partner block, rhs — the first factor's give the shape), 2-row
 // factors at even offsets only; the clique's rows are the panel's (n = panel rows, own rows first, hmap a permutation).
 constexpr int kStarMaxD = 3;

@@ -190,7 +190,7 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
   // then treats them as ordinary rows — the graph error gets mu e^2 / 2 for a violated constraint
   // (Constrained::squaredMahalanobisDistance, NoiseModel.cpp:438-444), the linearized error likewise
   // (JacobianFactor::error with the unit() model, JacobianFactor.cpp:508-513), and J'J a penalty term that is constant on
-  // the feasible set — and the factorization eliminates the rows EXACTLY by constraint pivots (solver.hip: constraint_*).
+  // the feasible set — and the factorization eliminates the rows EXACTLY by constraint pivots (solver.hip: dev_factorize launches the constraint_* kernels of constraint.hip).
   if (!P.con_factor.empty() || std::find(P.f_noise_kind.begin(), P.f_noise_kind.end(), (int)GSX_NOISE_CONSTRAINED) !=
                                    P.f_noise_kind.end()) {
     std::vector<double> noise;

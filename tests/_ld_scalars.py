@@ -37,7 +37,7 @@ import numpy as np
 
 from tests._ld_linear import LD, U
 
-CAP = 4096                                   # solver.hip:262 kPartials
+CAP = 4096                                   # handle.h: gsx_context::kPartials
 
 
 def _cdiv(a, b):
@@ -241,7 +241,7 @@ def _norm(v):
 
 def dogleg_expected(S, dx_n, radius, k_ax, k_dot):
     """(branch, expected point, bound on ||point - expected||_2) of DoglegOptimizerImpl::ComputeDoglegPoint as
-    gsx_dogleg_optimize evaluates it (solver.hip:2594-2611, :2678-2700), from the exact g = A'b, step = g'g / |A g|^2 and
+    gsx_dogleg_optimize evaluates it (optimizers.hip: dogleg_coefficients and the steepest-descent point of the iterate body), from the exact g = A'b, step = g'g / |A g|^2 and
     the backend's Newton step dx_n.
 
     First-order propagation of the derived relative errors, doubled for the second-order terms:

@@ -175,7 +175,7 @@ TIER_BOUNDS = (67, 140)
 
 def tree_shape(arr, ordering, amalgamation=DEEP_AMALGAMATION):
     """Host only: what the symbolic analysis makes of (arrays, ordering) — the figures the deep and wide cases are aimed
-    at.  Tree children / height / roots / tickets follow solver.hip's tables of the top-down launch (a tree front's tree
+    at.  Tree children / height / roots / tickets follow the tables of the top-down launch that upload_symbolic (upload.hip) builds (a tree front's tree
     children whatever their tier; tickets = roots + sum of max(children - 1, 0)); start fronts follow symbolic.cpp (no
     unfinished child in the front's own tier), with the tier restated from the largest front of the tree subtree."""
     from gtsam_petercdev_amd import _lib

@@ -1,12 +1,12 @@
 """Seeded LINEAR graphs for the scalar-reduction tests (test_host_scalar_judge.py, test_gpu_scalar_bounds.py): the smallest
 shapes that reach each edge of the linearized-error, damping and Dogleg reductions.  Every factor has the unit noise
-model, so its whitened [A b] is the block it was given (solver.hip: whiten_linear_factor copies it) and the host tests
+model, so its whitened [A b] is the block it was given (upload.hip: whiten_linear_factor copies it) and the host tests
 know the device's Jacobian array without a device: jacobian_array()."""
 import numpy as np
 
 from gtsam_petercdev_amd.graph import GaussianFactorGraph, JacobianFactor
 
-# solver.hip upload_problem (:452-463): the staged kernel's LDS slice is the largest [A b] range of 64 consecutive factors,
+# upload.hip, upload_problem: the staged kernel's LDS slice is the largest [A b] range of 64 consecutive factors,
 # rounded up to even, and 0 (the direct kernel) when two slices exceed 96 KB
 SLICE_LIMIT = 96 * 1024 // (2 * 8)          # 6144 doubles
 

@@ -15,7 +15,7 @@ neighbouring-lambda sequence on one handle, with bit-equal repeats.  These judge
 show a race in the hand-off and do not loop to look for one.
 
 gsx_get_conditional reports the factorization the arena holds: after solve(lambda, diag) the DAMPED one of that call
-(solver.hip: fact_lambda), after a marginal query the undamped one.  Measures (1) and (2) are therefore taken right after
+(handle.h: fact_lambda), after a marginal query the undamped one.  Measures (1) and (2) are therefore taken right after
 each solve, against Hd of that lambda; measure (3) does not depend on it.
 
 Every test prints its ratios in units of u (or of u kappa_2); the worst of the module are printed by the last test.
