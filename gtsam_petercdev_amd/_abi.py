@@ -19,6 +19,8 @@ GSX_OK, GSX_E_INVALID, GSX_E_NO_DEVICE, GSX_E_BAD_ORDERING, GSX_E_INDETERMINATE,
 VAR_VECTOR, VAR_POSE2, VAR_POSE3, VAR_CAMERA = range(4)
 F_LINEAR, F_PRIOR, F_BETWEEN, F_SFM, F_PROJECTION, F_BEARINGRANGE, F_RANGE, F_BEARING, F_STEREO, F_SFM2 = range(10)
 F_SMART_PROJECTION = 10
+F_TRANSLATION, F_BILINEAR_TRANSLATION = 11, 12   # gtsam/sfm/TranslationFactor.h
+MFAS_MAX_NODES = 8192    # GSX_MFAS_MAX_NODES
 SMART_MEAS_HEAD = 11   # doubles of a smart factor's meas before body_P_sensor / the pixels (include/gsx.h)
 NOISE_FORMAT_G2O, NOISE_FORMAT_TORO, NOISE_FORMAT_GRAPH, NOISE_FORMAT_COV, NOISE_FORMAT_AUTO = range(5)
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_CONSTRAINED = range(5)
@@ -144,6 +146,22 @@ class TriangulationParams(C.Structure):
     _fields_ = [("rank_tol", C.c_double), ("optimize", C.c_int32), ("use_lost", C.c_int32), ("noise_kind", C.c_int32),
                 ("noise", C.c_double * 5), ("landmark_distance_threshold", C.c_double),
                 ("dynamic_outlier_rejection_threshold", C.c_double), ("safe", C.c_int32)]
+
+
+class TranslationInput(C.Structure):
+    """gsx_translation_input: the measurements of TranslationRecovery::run."""
+    _fields_ = [("n_unit", C.c_int64), ("unit_key1", _p(C.c_uint64)), ("unit_key2", _p(C.c_uint64)),
+                ("unit_dirs", _p(C.c_double)), ("unit_noise_kind", _p(C.c_int32)), ("unit_noise_ptr", _p(C.c_int64)),
+                ("unit_noise", _p(C.c_double)), ("scale", C.c_double),
+                ("n_between", C.c_int64), ("between_key1", _p(C.c_uint64)), ("between_key2", _p(C.c_uint64)),
+                ("between_meas", _p(C.c_double)), ("between_noise_kind", _p(C.c_int32)), ("between_noise_ptr", _p(C.c_int64)),
+                ("between_noise", _p(C.c_double)),
+                ("n_given", C.c_int64), ("given_keys", _p(C.c_uint64)), ("given_values", _p(C.c_double))]
+
+
+class TranslationParams(C.Structure):
+    """gsx_translation_params: the members of TranslationRecovery and the seed of its generator."""
+    _fields_ = [("lm", LMParams), ("use_bilinear", C.c_int32), ("seed", C.c_uint32), ("prior_sigma", C.c_double)]
 
 
 # TriangulationResult::Status (triangulation.h:644) + the Cal3Bundler::calibrate failure

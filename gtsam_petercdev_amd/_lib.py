@@ -291,6 +291,8 @@ def _dataset_to_arrays(ds, meta) -> A.ProblemArrays:
     nv, nf = desc.n_vars, desc.n_factors
 
     def arr(ptr, n, dtype):
+        if int(n) == 0:      # (an empty vector hands out a null pointer: a problem without factors)
+            return np.zeros(0, dtype=dtype)
         return np.ctypeslib.as_array(ptr, shape=(max(int(n), 1),))[:int(n)].astype(dtype, copy=True)
     kp = arr(desc.f_key_ptr, nf + 1, np.int32)
     mp = arr(desc.f_meas_ptr, nf + 1, np.int64)
@@ -698,6 +700,129 @@ def triangulate_timings() -> dict:
     out = np.zeros(len(TRIANGULATE_TIMING_NAMES))
     _raise_init(f(A._dptr(out), C.c_int32(out.size)), "gsx_triangulate_timings")
     return dict(zip(TRIANGULATE_TIMING_NAMES, (float(x) for x in out)))
+
+
+# ---- translation averaging (include/gsx.h: gsx_mfas_*, gsx_translation_*) ------------------------------------------------
+def mfas_outlier_weights(key1, key2, edge_dirs=None, proj_dirs=None, weights=None, device: int = 0, want_weights: bool = True,
+                         want_ordering: bool = False) -> dict:
+    """gsx_mfas_outlier_weights: MFAS for D projection directions at once.  Either edge_dirs (E, 3) and proj_dirs (D, 3), or
+    weights (D, E).  Returns mean (E,), and when asked for weights (D, E) and ordering (D, n_nodes) keys."""
+    f = load().gsx_mfas_outlier_weights
+    f.restype = C.c_int32
+    k1 = np.ascontiguousarray(key1, dtype=np.uint64).reshape(-1)
+    k2 = np.ascontiguousarray(key2, dtype=np.uint64).reshape(-1)
+    if k1.shape != k2.shape:
+        raise ValueError("key1 and key2: one entry per edge")
+    ne = k1.size
+    if edge_dirs is not None:
+        ed = np.ascontiguousarray(edge_dirs, dtype=np.float64).reshape(-1, 3)
+        pd = np.ascontiguousarray(proj_dirs, dtype=np.float64).reshape(-1, 3)
+        if ed.shape[0] != ne:
+            raise ValueError("edge_dirs: three doubles per edge")
+        nd, w = pd.shape[0], None
+    else:
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1, max(ne, 1)) if ne else np.zeros((1, 1))
+        nd, ed, pd = w.shape[0], None, None
+    n_nodes = np.unique(np.concatenate([k1, k2])).size
+    mean = np.zeros(max(ne, 1))
+    ow = np.zeros((max(nd, 1), max(ne, 1))) if want_weights else None
+    oo = np.zeros((max(nd, 1), max(n_nodes, 1)), dtype=np.uint64) if want_ordering else None
+    kp = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+    st = f(kp(k1) if ne else None, kp(k2) if ne else None, C.c_int64(ne), None if ed is None else A._dptr(ed),
+           None if pd is None else A._dptr(pd), None if w is None else A._dptr(w), C.c_int32(nd), C.c_int32(device),
+           A._dptr(mean), None if ow is None else A._dptr(ow), None if oo is None else kp(oo))
+    _raise_init(st, "gsx_mfas_outlier_weights")
+    out = dict(mean=mean[:ne])
+    if want_weights:
+        out["weights"] = ow[:nd, :ne]
+    if want_ordering:
+        out["ordering"] = oo[:nd, :n_nodes]
+    return out
+
+
+MFAS_TIMING_NAMES = ("adjacency_host_ms", "mfas_ms", "mean_ms", "total_host_ms")
+
+
+def mfas_timings() -> dict:
+    """gsx_mfas_timings: the stage times of the last MFAS call of the process."""
+    f = load().gsx_mfas_timings
+    f.restype = C.c_int32
+    out = np.zeros(len(MFAS_TIMING_NAMES))
+    _raise_init(f(A._dptr(out), C.c_int32(out.size)), "gsx_mfas_timings")
+    return dict(zip(MFAS_TIMING_NAMES, (float(x) for x in out)))
+
+
+def translation_params_default() -> A.TranslationParams:
+    p = A.TranslationParams()
+    f = load().gsx_translation_params_default
+    f.restype = None
+    f(C.byref(p))
+    return p
+
+
+def _translation_input(unit, scale, between, given):
+    """gsx_translation_input and the arrays it points into.  unit / between: lists of (key1, key2, 3 doubles, noise kind,
+    noise parameters); given: {key: 3 doubles}."""
+    keep = []
+
+    def pack(edges):
+        k1 = np.array([e[0] for e in edges], dtype=np.uint64)
+        k2 = np.array([e[1] for e in edges], dtype=np.uint64)
+        z = np.array([np.asarray(e[2], dtype=float).reshape(3) for e in edges], dtype=np.float64).reshape(-1)
+        kind = np.array([e[3] for e in edges], dtype=np.int32)
+        params = [np.asarray(e[4], dtype=float).reshape(-1) for e in edges]
+        ptr = np.concatenate([[0], np.cumsum([q.size for q in params])]).astype(np.int64)
+        noise = np.concatenate(params + [np.zeros(1)])
+        keep.extend([k1, k2, z, kind, ptr, noise])
+        if not edges:
+            return 0, None, None, None, None, None, None
+        return (len(edges), k1.ctypes.data_as(C.POINTER(C.c_uint64)), k2.ctypes.data_as(C.POINTER(C.c_uint64)), A._dptr(z),
+                kind.ctypes.data_as(C.POINTER(C.c_int32)), ptr.ctypes.data_as(C.POINTER(C.c_int64)), A._dptr(noise))
+    u, b = pack(list(unit)), pack(list(between))
+    gk = np.array(sorted(given), dtype=np.uint64)
+    gv = np.array([np.asarray(given[int(k)], dtype=float).reshape(3) for k in gk], dtype=np.float64).reshape(-1)
+    keep.extend([gk, gv])
+    inp = A.TranslationInput(u[0], u[1], u[2], u[3], u[4], u[5], u[6], float(scale), b[0], b[1], b[2], b[3], b[4], b[5], b[6],
+                             gk.size, gk.ctypes.data_as(C.POINTER(C.c_uint64)) if gk.size else None,
+                             A._dptr(gv) if gk.size else None)
+    return inp, keep
+
+
+def translation_recovery_problem(unit, scale=1.0, between=(), given=None, params: A.TranslationParams = None):
+    """gsx_translation_recovery_problem (host): (ProblemArrays with the initial values, {merged key: its representative})."""
+    lib = load()
+    f = lib.gsx_translation_recovery_problem
+    f.restype = C.c_int32
+    lib.gsx_dataset_get.restype = C.c_int32
+    lib.gsx_dataset_free.restype = None
+    unit, between = list(unit), list(between)
+    inp, keep = _translation_input(unit, scale, between, given or {})
+    p = params if params is not None else translation_params_default()
+    n = max(2 * len(unit), 1)
+    mk, mi, nm = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_int64(0)
+    ds = C.c_void_p()
+    st = f(C.byref(inp), C.byref(p), C.byref(ds), mk.ctypes.data_as(C.POINTER(C.c_uint64)),
+           mi.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(nm))
+    _raise_init(st, "gsx_translation_recovery_problem")
+    arrays = _dataset_to_arrays(ds, dict(kind="translation"))
+    return arrays, {int(a): int(b) for a, b in zip(mk[:nm.value], mi[:nm.value])}
+
+
+def translation_recovery(unit, scale=1.0, between=(), given=None, params: A.TranslationParams = None, device: int = 0):
+    """gsx_translation_recovery: ({key: translation}, LM result dict)."""
+    f = load().gsx_translation_recovery
+    f.restype = C.c_int32
+    unit, between = list(unit), list(between)
+    inp, keep = _translation_input(unit, scale, between, given or {})
+    p = params if params is not None else translation_params_default()
+    n = max(2 * (len(unit) + len(between)), 1)
+    keys, out, n_out, r = np.zeros(n, np.uint64), np.zeros(3 * n), C.c_int64(0), A.LMResult()
+    st = f(C.byref(inp), C.byref(p), C.c_int32(device), keys.ctypes.data_as(C.POINTER(C.c_uint64)), A._dptr(out),
+           C.byref(n_out), C.byref(r))
+    _raise_init(st, "gsx_translation_recovery")
+    result = {int(k): out[3 * i:3 * i + 3].copy() for i, k in enumerate(keys[:n_out.value])}
+    return result, dict(initial_error=r.initial_error, final_error=r.final_error, final_lambda=r.final_lambda,
+                        iterations=r.iterations, inner_iterations=r.inner_iterations)
 
 
 def product_backend(arrays: A.ProblemArrays, device: int = 0) -> ProductBackend:

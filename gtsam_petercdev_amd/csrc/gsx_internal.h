@@ -7,6 +7,14 @@
 #include "../../include/gsx.h"
 
 struct gsx_context;
+// what gsx_dataset_get hands out (io.cpp: the file readers; translation_graph.cpp: gsx_translation_recovery_problem)
+struct gsx_dataset {
+  std::vector<uint64_t> var_keys;
+  std::vector<int32_t> var_types, var_dims, f_type, f_rows, f_key_ptr, f_vars, f_noise_kind;
+  std::vector<int64_t> f_meas_ptr, f_noise_ptr;
+  std::vector<double> meas, noise, values;
+  std::string err;
+};
 
 namespace gsx {
 

@@ -28,14 +28,6 @@
 
 #include "gsx_internal.h"
 
-struct gsx_dataset {
-  std::vector<uint64_t> var_keys;
-  std::vector<int32_t> var_types, var_dims, f_type, f_rows, f_key_ptr, f_vars, f_noise_kind;
-  std::vector<int64_t> f_meas_ptr, f_noise_ptr;
-  std::vector<double> meas, noise, values;
-  std::string err;
-};
-
 namespace {
 
 void quat_to_R(double w, double x, double y, double z, double* R) {  // row-major, Eigen's normalised convention

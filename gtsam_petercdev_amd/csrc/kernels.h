@@ -170,7 +170,9 @@ enum { TL_SFM = 0, TL_BETWEEN_POSE2 = 1, TL_BETWEEN_POSE3 = 2, TL_GENERIC = 3, T
        TL_PROJECTION_SENSOR = 12, TL_STEREO_SENSOR = 13, TL_RANGE_POSE2_POINT_SENSOR = 14, TL_RANGE_POSE2_POSE_SENSOR = 15,
        TL_RANGE_POSE3_POINT_SENSOR = 16, TL_RANGE_POSE3_POSE_SENSOR = 17, TL_SFM2 = 18,
        // SmartProjectionPoseFactor<Cal3_S2>: kernels of its own (smart.hip), and state the handle keeps (SmartDev)
-       TL_SMART = 19, kNumTypeLists = 20 };
+       TL_SMART = 19,
+       // TranslationFactor and BilinearAngleTranslationFactor (gtsam/sfm/TranslationFactor.h)
+       TL_TRANSLATION = 20, TL_BATA = 21, kNumTypeLists = 22 };
 constexpr int kSensorListShift = TL_RANGE_POSE2_POINT_SENSOR - TL_RANGE_POSE2_POINT;  // range list -> its sensor form
 // list of a factor of type `t` whose first two variables have types vt0, vt1 and whose measurement has nmeas doubles
 // (the sensor forms are told by their length); -1: GSX_F_LINEAR, no list
@@ -189,6 +191,8 @@ inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
     case GSX_F_BEARING: return TL_BEARING;
     case GSX_F_STEREO: return nmeas > 9 ? TL_STEREO_SENSOR : TL_STEREO;
     case GSX_F_SMART_PROJECTION: return TL_SMART;
+    case GSX_F_TRANSLATION: return TL_TRANSLATION;
+    case GSX_F_BILINEAR_TRANSLATION: return TL_BATA;
   }
   return TL_GENERIC;
 }

@@ -593,6 +593,60 @@ __global__ void __launch_bounds__(256) linearize_sfm2_kernel(DevProblem P, const
   whiten_store<2, 15>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
 }
 
+// TranslationFactor::evaluateError — gtsam/sfm/TranslationFactor.h:68-78: e = normalize(Tb - Ta) - z with the derivative
+// of normalize (gtsam/geometry/Point3.cpp:52-62), H1 = -H2.  Ta == Tb divides by zero, as there: no special case
+__global__ void __launch_bounds__(256) linearize_translation_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                    double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+  const double* ta = values + fr.s0;
+  const double* tb = values + fr.s1;
+  const double* z = P.meas + fr.meas_off;
+  const double x = tb[0] - ta[0], y = tb[1] - ta[1], w = tb[2] - ta[2];
+  const double x2 = x * x, y2 = y * y, z2 = w * w, n2 = x2 + y2 + z2, nrm = sqrt(n2), n3 = n2 * nrm;
+  double H[9] = {(y2 + z2) / n3, -(x * y) / n3, -(x * w) / n3, 0, (x2 + z2) / n3, -(y * w) / n3, 0, 0, (x2 + y2) / n3}, J[21];
+  H[3] = H[1]; H[6] = H[2]; H[7] = H[5];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {  // (symmetric: row- and column-major agree)
+    J[k] = -H[k];
+    J[9 + k] = H[k];
+  }
+  J[18] = z[0] - x / nrm;  // b = -e
+  J[19] = z[1] - y / nrm;
+  J[20] = z[2] - w / nrm;
+  whiten_store<3, 7>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+
+// BilinearAngleTranslationFactor::evaluateError — gtsam/sfm/TranslationFactor.h:133-149: keys (Ta, Tb, scale); e =
+// |s| (Tb - Ta) - z, H1 = -|s| I, H2 = |s| I, H3 = Tb - Ta for s >= 0 (zero included), else Ta - Tb
+__global__ void __launch_bounds__(256) linearize_bata_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                             double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int f = list[i];
+  const FactorRec fr = P.frec[f];
+  const double* ta = values + fr.s0;
+  const double* tb = values + fr.s1;
+  const double s = values[P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]]];  // (the record holds two state offsets)
+  const double* z = P.meas + fr.meas_off;
+  const double a = fabs(s), d[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
+  double J[24];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      J[3 * c + r] = (r == c) ? -a : 0.0;
+      J[9 + 3 * c + r] = (r == c) ? a : 0.0;
+    }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    J[18 + r] = s >= 0 ? d[r] : -d[r];
+    J[21 + r] = z[r] - d[r] * a;  // b = -e
+  }
+  whiten_store<3, 8>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+
 void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
                       const double* values, double* jac, DevStatus* status, hipStream_t st, const SmartDev* smart) {
   auto grid = [](int n) { return dim3((n + 255) / 256); };
@@ -643,6 +697,8 @@ void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeL
   run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR, true>, TL_RANGE_POSE3_POINT_SENSOR);
   run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3, true>, TL_RANGE_POSE3_POSE_SENSOR);
   run_s(linearize_sfm2_kernel, TL_SFM2);
+  run(linearize_translation_kernel, TL_TRANSLATION);
+  run(linearize_bata_kernel, TL_BATA);
   if (type_counts[TL_SMART] && smart) {   // triangulate (cache consulted and updated), then marginalize the landmark
     launch_smart_triangulate(P, type_lists[TL_SMART], type_counts[TL_SMART], values, *smart, st);
     launch_smart_linearize(P, type_lists[TL_SMART], type_counts[TL_SMART], *smart, jac, st);
@@ -762,6 +818,20 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
     e[1] = pi[1] - z[1];
     return whitened_half_sqnorm<2>(e, kind, np);
   }
+  if constexpr (FT == GSX_F_TRANSLATION) {  // normalize(Tb - Ta) - z (gtsam/sfm/TranslationFactor.h:68-78)
+    const double* ta = values + fr.s0;
+    const double* tb = values + fr.s1;
+    const double x = tb[0] - ta[0], y = tb[1] - ta[1], w = tb[2] - ta[2], nrm = sqrt(x * x + y * y + w * w);
+    double e[3] = {x / nrm - z[0], y / nrm - z[1], w / nrm - z[2]};
+    return whitened_half_sqnorm<3>(e, kind, np);
+  }
+  if constexpr (FT == GSX_F_BILINEAR_TRANSLATION) {  // |s| (Tb - Ta) - z (:133-149)
+    const double* ta = values + fr.s0;
+    const double* tb = values + fr.s1;
+    const double a = fabs(values[P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]]]);
+    double e[3] = {(tb[0] - ta[0]) * a - z[0], (tb[1] - ta[1]) * a - z[1], (tb[2] - ta[2]) * a - z[2]};
+    return whitened_half_sqnorm<3>(e, kind, np);
+  }
   const int vt = FV >= 0 ? FV : ((fr.type_kind >> 24) & 0xff);
   if (type == GSX_F_BETWEEN && vt == GSX_VAR_POSE2) {
     const P2 h = compose(inverse(load_pose2(values + fr.s0)), load_pose2(values + fr.s1));
@@ -841,8 +911,11 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
   // the sensor forms and GSX_F_SFM2 keeps the shares — hence the summation order, hence the bits — it had before they came
   bool new_lists = false;
   for (int k = TL_PROJECTION_SENSOR; k < TL_SMART; ++k) new_lists = new_lists || type_counts[k] > 0;
-  // (likewise a graph without smart factors keeps the shares it had before TL_SMART came)
-  const int held = type_counts[TL_SMART] > 0 ? kNumTypeLists : (new_lists ? TL_SMART : TL_PROJECTION_SENSOR);
+  // (likewise a graph without smart factors keeps the shares it had before TL_SMART came, and one without the translation
+  // factors those it had before TL_TRANSLATION and TL_BATA came)
+  const int held = type_counts[TL_TRANSLATION] + type_counts[TL_BATA] > 0
+                       ? kNumTypeLists
+                       : (type_counts[TL_SMART] > 0 ? TL_TRANSLATION : (new_lists ? TL_SMART : TL_PROJECTION_SENSOR));
   int off = 0;
   for (int k = 0; k < kNumTypeLists; ++k) {
     const int n = type_counts[k];
@@ -870,6 +943,8 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
       case TL_RANGE_POSE3_POINT_SENSOR:
       case TL_RANGE_POSE3_POSE_SENSOR: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_SFM2: error_list_kernel<GSX_F_SFM2, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_TRANSLATION: error_list_kernel<GSX_F_TRANSLATION, GSX_VAR_VECTOR><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_BATA: error_list_kernel<GSX_F_BILINEAR_TRANSLATION, GSX_VAR_VECTOR><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_SMART:   // triangulate at `values` (cache consulted and updated), then the reprojection errors
         launch_smart_triangulate(P, type_lists[k], n, values, *smart, st);
         launch_smart_error(P, type_lists[k], n, *smart, out, nb, st);

@@ -135,6 +135,14 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
         }
         break;
       }
+      case GSX_F_TRANSLATION:
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_VECTOR && dv(0) == 3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && m == 3 &&
+             nmeas == 3;
+        break;
+      case GSX_F_BILINEAR_TRANSLATION:
+        ok = ok && nk == 3 && tv(0) == GSX_VAR_VECTOR && dv(0) == 3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 &&
+             tv(2) == GSX_VAR_VECTOR && dv(2) == 1 && m == 3 && nmeas == 3;
+        break;
       default:
         ok = false;
     }

@@ -518,6 +518,50 @@ def GeneralSFMFactor2(measured, model, poseKey, landmarkKey, calibKey):
 GeneralSFMFactor2Cal3_S2 = GeneralSFMFactor2
 
 
+class Unit3:
+    """gtsam/geometry/Unit3.h, minimal: the constructor normalises (Unit3.h:70-79) and leaves (0, 0, 0) alone — it is what
+    TranslationRecovery compares zero-translation edges against (TranslationRecovery.cpp:55)."""
+
+    def __init__(self, *args):
+        if len(args) == 0:
+            p = np.array([1.0, 0.0, 0.0])
+        elif len(args) == 1:
+            p = args[0].p.copy() if isinstance(args[0], Unit3) else np.asarray(args[0], dtype=float).reshape(3).copy()
+        else:
+            p = np.array([float(a) for a in args]).reshape(3)
+        n = math.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2])
+        self.p = p / n if n > 0 else p
+
+    def point3(self):
+        return self.p.copy()
+
+    unitVector = point3
+
+    def dot(self, q: "Unit3") -> float:
+        return float(self.p[0] * q.p[0] + self.p[1] * q.p[1] + self.p[2] * q.p[2])
+
+    def equals(self, q: "Unit3", tol=1e-9) -> bool:
+        return bool(np.all(np.abs(self.p - q.p) <= tol))
+
+    def __repr__(self):
+        return f"Unit3({self.p[0]:.6g}, {self.p[1]:.6g}, {self.p[2]:.6g})"
+
+
+def _direction(w_aZb) -> np.ndarray:
+    return w_aZb.point3() if isinstance(w_aZb, Unit3) else Unit3(w_aZb).point3()
+
+
+def TranslationFactor(a, b, w_aZb, model=None):
+    """TranslationFactor(a, b, w_aZb, noiseModel) — gtsam/sfm/TranslationFactor.h:41-78: normalize(Tb - Ta) - w_aZb."""
+    return _Factor(A.F_TRANSLATION, [a, b], 3, _direction(w_aZb), model)
+
+
+def BilinearAngleTranslationFactor(a, b, scaleKey, w_aZb, model=None):
+    """BilinearAngleTranslationFactor(a, b, scale_key, w_aZb, noiseModel) — TranslationFactor.h:104-149 (BATA):
+    |s| (Tb - Ta) - w_aZb with the scale a Vector1 variable."""
+    return _Factor(A.F_BILINEAR_TRANSLATION, [a, b, scaleKey], 3, _direction(w_aZb), model)
+
+
 class Cal3_S2Stereo:
     """gtsam/geometry/Cal3_S2Stereo.h: (fx, fy, s, u0, v0, b)."""
 
@@ -930,6 +974,160 @@ class lago:
             arr, _, _ = lago._lower(pg)
             packed = _lib.lago_initialize(arr, bool(useOdometricPathOrInitialGuess))
         return Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, packed)
+
+
+# ---- translation averaging: 1dSfM (gtsam/sfm/MFAS.h, TranslationRecovery.h) on the device: include/gsx.h gsx_mfas_*, gsx_translation_* ----
+class _BinaryMeasurement:
+    """gtsam/sfm/BinaryMeasurement.h."""
+
+    def __init__(self, key1, key2, measured, model=None):
+        self.key1_, self.key2_, self.measured_ = int(key1), int(key2), measured
+        self.model_ = model if model is not None else noiseModel.Unit.Create(3)
+
+    def key1(self): return self.key1_
+    def key2(self): return self.key2_
+    def measured(self): return self.measured_
+    def noiseModel(self): return self.model_
+
+
+class BinaryMeasurementUnit3(_BinaryMeasurement):
+    def __init__(self, key1, key2, measured, model=None):
+        super().__init__(key1, key2, measured if isinstance(measured, Unit3) else Unit3(measured), model)
+
+    def vector(self):
+        return self.measured_.point3()
+
+
+class BinaryMeasurementPoint3(_BinaryMeasurement):
+    def __init__(self, key1, key2, measured, model=None):
+        super().__init__(key1, key2, np.asarray(measured, dtype=float).reshape(3).copy(), model)
+
+    def vector(self):
+        return self.measured_.copy()
+
+
+class MFAS:
+    """gtsam/sfm/MFAS.h: MFAS(relativeTranslations, projectionDirection) or MFAS(edgeWeights); the D = 1 case of the batched
+    device entry (gsx_mfas_outlier_weights).  The ordering is *a* valid MFAS ordering: among several roots the lowest key
+    comes first, where the reference takes the first in unordered_map order (include/gsx.h)."""
+
+    def __init__(self, *args):
+        if len(args) == 2:
+            relativeTranslations, direction = args
+            d = direction if isinstance(direction, Unit3) else Unit3(direction)
+            self.edgeWeights_ = {}
+            for m in relativeTranslations:   # (a repeated pair keeps the last entry: the map assignment of MFAS.cpp:119)
+                self.edgeWeights_[(m.key1(), m.key2())] = m.measured().dot(d)
+        else:
+            self.edgeWeights_ = {(int(a), int(b)): float(w) for (a, b), w in dict(args[0]).items()}
+
+    def _run(self, want_ordering):
+        from . import _lib
+        pairs = list(self.edgeWeights_)
+        w = np.array([[self.edgeWeights_[p] for p in pairs]])
+        return pairs, _lib.mfas_outlier_weights([p[0] for p in pairs], [p[1] for p in pairs], weights=w,
+                                                want_ordering=want_ordering)
+
+    def computeOrdering(self) -> List[Key]:
+        if not self.edgeWeights_:
+            return []
+        return [int(k) for k in self._run(True)[1]["ordering"][0]]
+
+    def computeOutlierWeights(self) -> Dict[Tuple[Key, Key], float]:
+        if not self.edgeWeights_:
+            return {}
+        pairs, out = self._run(False)
+        return {p: float(x) for p, x in zip(pairs, out["weights"][0])}
+
+    @staticmethod
+    def outlierWeightsBatch(measurements, directions) -> dict:
+        """The batched entry: every measurement projected along every direction (D workgroups in one launch).  Returns
+        {"pairs": [(key1, key2)], "weights": (D, E), "mean": (E,)} in the order of `measurements`; mean[e] = sum over d of
+        weights[d][e] / D, the average of python/gtsam/examples/TranslationAveragingExample.py:84-87."""
+        from . import _lib
+        ms = list(measurements)
+        dirs = np.array([(d if isinstance(d, Unit3) else Unit3(d)).point3() for d in directions]).reshape(-1, 3)
+        out = _lib.mfas_outlier_weights([m.key1() for m in ms], [m.key2() for m in ms],
+                                        edge_dirs=np.array([m.measured().point3() for m in ms]).reshape(-1, 3), proj_dirs=dirs)
+        return dict(pairs=[(m.key1(), m.key2()) for m in ms], weights=out["weights"], mean=out["mean"])
+
+
+class TranslationRecovery:
+    """gtsam/sfm/TranslationRecovery.h: TranslationRecovery(lmParams) / TranslationRecovery(lmParams,
+    use_bilinear_translation_factor).  run() goes through gsx_translation_recovery; buildGraph / addPrior /
+    initializeRandomly are the reference's building blocks on this mirror's graph classes (initializeRandomly draws from
+    gsx_translation_recovery_problem, so the stream is the library's: std::mt19937(seed), fresh per call)."""
+
+    def __init__(self, lmParams=None, use_bilinear_translation_factor=False, seed=42):
+        self.lmParams_ = lmParams if lmParams is not None else LevenbergMarquardtParams()
+        self.use_bilinear_translation_factor_ = bool(use_bilinear_translation_factor)
+        self.seed_ = int(seed)
+
+    def _params(self) -> A.TranslationParams:
+        from . import _lib
+        p = _lib.translation_params_default()
+        p.lm = self.lmParams_.c_params()
+        p.use_bilinear = int(self.use_bilinear_translation_factor_)
+        p.seed = self.seed_
+        return p
+
+    @staticmethod
+    def _edges(ms):
+        return [(m.key1(), m.key2(), m.vector(), m.noiseModel().kind, m.noiseModel().params) for m in ms]
+
+    def buildGraph(self, relativeTranslations) -> "NonlinearFactorGraph":
+        graph = NonlinearFactorGraph()
+        for i, edge in enumerate(relativeTranslations):
+            if self.use_bilinear_translation_factor_:
+                graph.add(BilinearAngleTranslationFactor(edge.key1(), edge.key2(), symbol("S", i), edge.measured(),
+                                                         edge.noiseModel()))
+            else:
+                graph.add(TranslationFactor(edge.key1(), edge.key2(), edge.measured(), edge.noiseModel()))
+        return graph
+
+    def addPrior(self, relativeTranslations, scale, betweenTranslations, graph, priorNoiseModel=None):
+        relativeTranslations = list(relativeTranslations)
+        if not relativeTranslations:
+            return
+        edge = relativeTranslations[0]
+        prior = priorNoiseModel if priorNoiseModel is not None else noiseModel.Isotropic.Sigma(3, 0.01)
+        graph.add(PriorFactor(edge.key1(), Point3(0, 0, 0), prior))
+        betweenTranslations = list(betweenTranslations)
+        if not betweenTranslations:
+            graph.add(PriorFactor(edge.key2(), scale * edge.measured().point3(), edge.noiseModel()))
+            return
+        for b in betweenTranslations:
+            graph.add(BetweenFactor(b.key1(), b.key2(), b.measured(), b.noiseModel()))
+
+    def initializeRandomly(self, relativeTranslations, betweenTranslations=(), initialValues=None) -> "Values":
+        from . import _lib
+        given = {} if initialValues is None else {k: initialValues.at(k) for k in initialValues.keys()}
+        # (the edges as they are: a zero direction merges nodes in run(), not here — keep it from merging by asking for the
+        # values of the keys alone: the draws depend on the order of first appearance only)
+        rel = [(m.key1(), m.key2(), np.array([1.0, 0.0, 0.0]), A.NOISE_UNIT, ()) for m in relativeTranslations]
+        btw = [(m.key1(), m.key2(), np.zeros(3), A.NOISE_UNIT, ()) for m in betweenTranslations]
+        arr, _ = _lib.translation_recovery_problem(rel, 1.0, btw, given, self._params())
+        return Values.unpack(arr.var_keys, arr.var_types, arr.var_dims, arr.values)
+
+    def run(self, relativeTranslations, scale=1.0, betweenTranslations=(), initialValues=None) -> "Values":
+        from . import _lib
+        given = {} if initialValues is None else {k: initialValues.at(k) for k in initialValues.keys()}
+        result, self.lastResult_ = _lib.translation_recovery(self._edges(relativeTranslations), scale,
+                                                             self._edges(betweenTranslations), given, self._params())
+        out = Values()
+        for k in sorted(result):
+            out.insert(k, result[k])
+        return out
+
+    @staticmethod
+    def SimulateMeasurements(poses: "Values", edges) -> List[BinaryMeasurementUnit3]:
+        """TranslationRecovery::SimulateMeasurements (TranslationRecovery.cpp:230-243)."""
+        model = noiseModel.Isotropic.Sigma(3, 0.01)
+        out = []
+        for a, b in edges:
+            Ta, Tb = poses.at(a).translation(), poses.at(b).translation()
+            out.append(BinaryMeasurementUnit3(a, b, Unit3(np.asarray(Tb) - np.asarray(Ta)), model))
+        return out
 
 
 # ---- triangulation (gtsam/geometry/triangulation.h) on the device: include/gsx.h gsx_triangulate* --------------------------

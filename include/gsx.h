@@ -166,7 +166,7 @@ enum {
                                (Cal3_S2.cpp:54-62).  Cheirality (:270-277): zero
                                Jacobians and a ZERO error — not the 2 fx of
                                GSX_F_PROJECTION — counted in n_cheirality          */
-  GSX_F_SMART_PROJECTION = 10 /* SmartProjectionPoseFactor<Cal3_S2> (gtsam/slam/SmartProjectionPoseFactor.h,
+  GSX_F_SMART_PROJECTION = 10, /* SmartProjectionPoseFactor<Cal3_S2> (gtsam/slam/SmartProjectionPoseFactor.h,
                                SmartProjectionFactor.h, SmartFactorBase.h): one factor per track.  At every
                                linearization it triangulates the landmark from the current poses (triangulateSafe, DLT,
                                no noise model; the LM refinement with enable_epi), marginalizes it and hands the
@@ -187,6 +187,17 @@ enum {
                                return GSX_E_INVALID — the reference's SmartProjectionRigFactor makes the same restriction.
                                No linearization mode is offered: HESSIAN and JACOBIAN_SVD give the same normal equations
                                at lambda = 0, which is what NonlinearFactorGraph::linearize passes                   */
+  GSX_F_TRANSLATION = 11,   /* TranslationFactor (gtsam/sfm/TranslationFactor.h:41-78); keys (VECTOR(3), VECTOR(3)) =
+                               (Ta, Tb); m = 3; meas = the 3 doubles of w_aZb.point3(), taken as given (the ABI does not
+                               renormalise; the Python Unit3 normalises as the reference's constructor does).  Error =
+                               normalize(Tb - Ta) - z; H2 = the 3 x 3 derivative of normalize (gtsam/geometry/
+                               Point3.cpp:52-62), H1 = -H2.  Ta == Tb divides by zero exactly as the reference does: no
+                               special case — the non-finite block surfaces through the handle's existing non-finite
+                               reporting (a failed factorization / GSX_E_INDETERMINATE, a non-finite error)            */
+  GSX_F_BILINEAR_TRANSLATION = 12 /* BilinearAngleTranslationFactor (TranslationFactor.h:104-149), BATA; keys (VECTOR(3),
+                               VECTOR(3), VECTOR(1)) = (Ta, Tb, scale); m = 3; meas = the same 3 doubles.  Error =
+                               |s| (Tb - Ta) - z; H1 = -|s| I, H2 = |s| I, H3 = (Tb - Ta) for s >= 0 — s == 0 takes this
+                               branch — else (Ta - Tb)                                                                 */
 };
 
 /* ---- noise model kinds (gtsam/linear/NoiseModel.cpp) --------------------- */
@@ -940,6 +951,96 @@ gsx_status gsx_triangulate_timings(double* out_ms, int32_t n);
  * status_out [n]; either array may be NULL.  n must be the number of smart factors of the graph (GSX_E_INVALID otherwise;
  * n = 0 with no smart factor is GSX_OK). */
 gsx_status gsx_smart_points(gsx_handle h, double* points_out, int32_t* status_out, int64_t n);
+
+/* ---- Translation averaging: 1dSfM (gtsam/sfm/MFAS.{h,cpp}, gtsam/sfm/TranslationRecovery.{h,cpp}) ----------------------------
+ * MFAS (minimum feedback arc set, MFAS.cpp:36-171) for n_dirs projection directions at once over one edge set
+ * (csrc/mfas.hip): one workgroup per direction, the node sums in LDS.
+ *   edges: n_edges unordered pairs (key1[i], key2[i]); a pair given twice in the same order keeps the LAST entry (the map
+ *     assignment of MFAS.cpp:119); a pair present in both orders, or key1[i] == key2[i], is GSX_E_INVALID (absWeightOfEdge
+ *     :85-91 cannot tell the two orders apart).
+ *   weights: either edge_dirs (3 per edge) and proj_dirs (3 per direction): w[d][e] = edge_dirs[e] . proj_dirs[d]
+ *     (:118-121, summed x, y, z in that order without fused multiply-add), or, with edge_dirs == NULL, `weights`
+ *     [n_dirs x n_edges] given (the MFAS(edgeWeights) constructor).  The entry of a superseded duplicate is ignored.
+ *   out_mean[e] = sum over d, in order of d, of out_weights[d][e] / n_dirs (python/gtsam/examples/
+ *     TranslationAveragingExample.py:84-87); out_weights [n_dirs x n_edges] or NULL; out_ordering [n_dirs x n_nodes] keys or
+ *     NULL, n_nodes = the distinct keys of the edges.  A superseded duplicate gets its successor's values.
+ * The ordering: the reference removes "the first root in unordered_map order", which is unspecified.  Any order among the
+ * roots (in-weight sum < 1e-8) gives the same outlier weights apart from edges with |w| < 1e-8, so out_ordering is *a* valid
+ * MFAS ordering, defined here as: the root of the lowest key first; without a root the node of the largest (out + 1) /
+ * (in + 1), the lowest key on an exact tie.  No atomics: two runs give the same bits.
+ * LIMIT: at most GSX_MFAS_MAX_NODES = 8192 distinct keys — two doubles and a flag byte of LDS per node, 136 KiB of the
+ * 160 KiB of a gfx950 workgroup — and n_dirs x n_edges below 2^31.  Above:
+ * GSX_E_INVALID with a line on stderr, never a skipped launch.  Every GSX_E_INVALID of the arguments comes before a device
+ * is touched; the launcher's own LDS check (dynamic + static LDS of the kernel against 160 KiB) follows the device check and
+ * cannot fire within the node limit.
+ * The launch takes min(n_dirs, CUs x resident workgroups per CU) workgroups, each striding over the directions.  The
+ * environment variable GSX_MFAS_MAX_GRID (a positive integer, read at every call) caps that number: a tuning and test
+ * knob — the outputs are the same bits at any grid. */
+#define GSX_MFAS_MAX_NODES 8192
+gsx_status gsx_mfas_outlier_weights(const uint64_t* key1, const uint64_t* key2, int64_t n_edges,
+                                    const double* edge_dirs, const double* proj_dirs, const double* weights,
+                                    int32_t n_dirs, int32_t device, double* out_mean, double* out_weights,
+                                    uint64_t* out_ordering);
+/* Stage times (ms) of the LAST MFAS call of the process (not thread-safe; for tools/translation_probe.py), n = 4: [0] host:
+ * key ranking, duplicate handling, CSR; [1] mfas_kernel; [2] mfas_mean_kernel; [3] the whole call on the host clock,
+ * transfers included.  [1]-[2] are HIP events. */
+gsx_status gsx_mfas_timings(double* out_ms, int32_t n);
+
+/* TranslationRecovery (TranslationRecovery.cpp:49-228).  The measurements: n_unit direction edges (keys, 3 doubles each —
+ * taken as given — and a noise model each: GSX_NOISE_* kind and a CSR of parameters sized for m = 3), `scale`, n_between
+ * BinaryMeasurement<Point3> edges in the same layout, and n_given initial translations (keys + 3 doubles each). */
+typedef struct gsx_translation_input {
+  int64_t n_unit;
+  const uint64_t *unit_key1, *unit_key2;
+  const double* unit_dirs;            /* [3 n_unit] */
+  const int32_t* unit_noise_kind;     /* [n_unit] */
+  const int64_t* unit_noise_ptr;      /* [n_unit + 1] CSR into unit_noise */
+  const double* unit_noise;
+  double scale;
+  int64_t n_between;
+  const uint64_t *between_key1, *between_key2;
+  const double* between_meas;         /* [3 n_between] */
+  const int32_t* between_noise_kind;
+  const int64_t* between_noise_ptr;
+  const double* between_noise;
+  int64_t n_given;
+  const uint64_t* given_keys;
+  const double* given_values;         /* [3 n_given] */
+} gsx_translation_input;
+typedef struct gsx_translation_params {
+  gsx_lm_params lm;            /* default: gsx_lm_params_legacy (TranslationRecovery() default-constructs LevenbergMarquardtParams) */
+  int32_t use_bilinear;        /* BATA: one VECTOR(1) scale variable Symbol('S', i) per kept edge, initial value 1 */
+  uint32_t seed;               /* std::mt19937 seed of the random initial values; default 42 (TranslationRecovery.cpp:42) */
+  double prior_sigma;          /* isotropic sigma of the origin prior; default 0.01 (TranslationRecovery.h:111-112) */
+} gsx_translation_params;
+void gsx_translation_params_default(gsx_translation_params* p);
+/* Host only, needs no device: the graph and initial values TranslationRecovery::run builds (csrc/translation_graph.cpp).
+ *   - zero edges merged: union-find over the unit edges whose direction has every component within 1e-9 of 0
+ *     (Unit3::equals against Unit3(0, 0, 0), :49-60); every edge of both lists is rewritten onto the representatives and
+ *     dropped when its ends coincide (:65-76).  The representative of a set is the root DSFMap gives it: union by rank,
+ *     the root of key1 on a tie (gtsam/base/DSFMap.h:87-102).
+ *   - factors in edge order: GSX_F_TRANSLATION, or with use_bilinear GSX_F_BILINEAR_TRANSLATION with the scale variable
+ *     Symbol('S', i) = ('S' << 56 | i), i counting the KEPT edges (buildGraph, :99-117);
+ *   - priors (addPrior, :119-143): GSX_F_PRIOR at the origin on the first kept edge's key1 (Isotropic prior_sigma); without
+ *     between edges a GSX_F_PRIOR scale * z on that edge's key2 with that edge's noise; otherwise one GSX_F_BETWEEN on
+ *     VECTOR(3) per kept between edge;
+ *   - initial values (initializeRandomly, :145-181): in first-appearance order over the kept unit edges, then the kept between
+ *     edges, each key takes its given value or three draws of std::uniform_real_distribution<double>(-1, 1) from
+ *     std::mt19937(seed); scale variables start at 1.  A FRESH generator is made per call: the reference's static generator
+ *     gives this stream on its first call in a process and continues it on later ones.
+ *   - no kept edge of either list: no factors, one origin value per set of the union-find (:216-223).
+ * The result is a gsx_dataset, read with gsx_dataset_get and released with gsx_dataset_free; variables in ascending key order.  merged_keys /
+ * merged_into (each with room for 2 n_unit entries, or NULL): every key of a merged set that is not its representative, and
+ * that representative; *n_merged their number. */
+gsx_status gsx_translation_recovery_problem(const gsx_translation_input* in, const gsx_translation_params* p, gsx_dataset** out,
+                                            uint64_t* merged_keys, uint64_t* merged_into, int64_t* n_merged);
+/* TranslationRecovery::run (:191-228): the description above on an ordinary handle, gsx_lm_optimize with p->lm, and the
+ * values read back — no solver code of its own.  keys_out / translations_out (3 per key): the translation variables in
+ * ascending key order followed by the merged keys, each with its representative's result (addSameTranslationNodes, :80-97);
+ * room for 2 (n_unit + n_between) keys always suffices; *n_out their number.  r (may be NULL): the LM result; without a kept
+ * edge no handle is created, no device is needed and r is zeroed. */
+gsx_status gsx_translation_recovery(const gsx_translation_input* in, const gsx_translation_params* p, int32_t device,
+                                    uint64_t* keys_out, double* translations_out, int64_t* n_out, gsx_lm_result* r);
 
 /* ---- dense kernel exposed for unit parity (gtsam/base/cholesky.cpp:108-159) -- */
 /* In-place partial Cholesky of an n x n column-major symmetric matrix (upper
