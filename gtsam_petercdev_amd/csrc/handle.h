@@ -127,6 +127,13 @@ struct Context {
   DevBuf<VarRec> d_fvar_recs;
   DevBuf<LeafRec> d_leaf_recs;   // leaf-kernel cliques of level 0, in schedule order
   int leaf_base = 0;             // schedule position of d_leaf_recs[0]
+  // The back-substitution solves narrow leaf cliques several to a wave (kernels.hip: backsolve_leaf_packed): its own copy
+  // of d_leaf_recs, partitioned into the 16-lane, 32-lane and wave classes with the order inside a class kept
+  // (leaf_bs_n: their sizes; all 0: no clique shares a wave and d_leaf_recs serves).  GSX_BS_LEAF_PACK=0 at gsx_create:
+  // a wave per clique.
+  bool bs_leaf_pack_env = true;  // (read once per handle)
+  DevBuf<LeafRec> d_leaf_bs_recs;
+  int leaf_bs_n[3] = {0, 0, 0};
   int lin_err_slice = 0;         // LDS doubles per wave of the staged linear-error kernel (0: blocks too large, direct kernel)
   DevBuf<int> d_fr_N, d_fr_F, d_fr_nfv, d_fr_fvar_ptr, d_fvars, d_fr_parent, d_fr_lean, d_fr_child_ptr, d_children, d_cmap,
       d_gidx, d_h_rows, d_hmap, d_h_loc, d_sched, d_hvars;

@@ -52,6 +52,15 @@ struct LeafRec {
   int dA, rows, loc, toff;
   int fvar_ptr, front, pad0, pad1;
 };
+// The three classes of a leaf back-substitution launch (backsolve_leaf_kernel): cliques and workgroups of each
+struct LeafPack {
+  int n16, n32, n64, nb16, nb32;
+};
+// Separator rows a lane of a shared wave keeps in registers: a clique takes 16 lanes up to 64 separator rows, 32 lanes up
+// to 128 (the rows the wave form keeps in registers), else the wave.  (2 rows a lane — 32 / 64 rows, the registers of the
+// wave form — measured 59.1 us a launch on bal1723 against 53.6 us: profiles/README.md, r06.)
+constexpr int kLeafPackRows = 4;
+static_assert(16 * kLeafPackRows <= 64 && 32 * kLeafPackRows <= 128, "classes of backsolve_leaf_packed");
 // A STAR LEAF (front_star_leaf_kernel): a lean, childless clique whose one frontal variable is of the star group of the
 // H assembly (every BAL landmark, upload.hip: upload_symbolic).  Its factor blocks are read straight from [A b] through
 // the variable's term records (three per factor: own block, partner block, rhs — the first factor's give the shape), 2-row
@@ -353,9 +362,13 @@ struct WildfireArgs {
 void launch_mark_fronts(const int* ids, int count, unsigned char* flags, hipStream_t st);
 void launch_wildfire_post(const DevSymbolic& S, const int* ids, int count, bool wave_per_clique, const WildfireArgs& W,
                           double* delta, hipStream_t st);
-// leaf cliques of a level, a wave per clique
-void launch_backsolve_leaf(const DevSymbolic& S, const LeafRec* recs, int count, int max_F, const double* arena,
-                           double* delta, DevStatus* status, hipStream_t st);
+// leaf cliques of a level in one launch: recs holds n16 cliques solved four to a wave (16 lanes each), then n32 solved two
+// to a wave, then n64 solved a wave each.  leaf_pack_class: the lanes a clique of n rows and F columns gets in a launch
+// whose widest clique has max_F columns — the narrowest group whose kLeafPackRows register rows a lane cover the separator
+// and whose lanes hold the F x F triangle
+int leaf_pack_class(int n, int F, int max_F);
+void launch_backsolve_leaf(const DevSymbolic& S, const LeafRec* recs, int n16, int n32, int n64, int max_F,
+                           const double* arena, double* delta, DevStatus* status, hipStream_t st);
 // Dogleg (gtsam/nonlinear/DoglegOptimizerImpl.*): gradient g = A'b out of the H panels' rhs rows, |A x|^2 over the
 // linearized graph, dot products and out = alpha a + beta b on tangent vectors (deterministic two-stage reductions)
 void launch_gradient(const DevProblem& P, const DevSymbolic& S, const double* H, double* g, hipStream_t st);

@@ -3643,11 +3643,13 @@ __global__ void backsolve_kernel(DevSymbolic S, const int* ids, const double* ar
 // clique's record — the row indices, the rows of L21 for the first 128 separator rows, the rhs row, the F x F
 // triangle — is requested together; the parents' solution is the second round trip, the store the third.
 // FM = the launch's largest F rounded up (register arrays are sized by it).
+// This is the WAVE FORM, for the cliques leaf_pack_class sends to 64 lanes (more than 128 separator rows — the tail loop
+// below — or a triangle of more than 32 entries) and for every clique of a handle made under GSX_BS_LEAF_PACK=0; the others
+// share a wave (backsolve_leaf_packed below), with this form's bits.
 template <int FM>
-__global__ void __launch_bounds__(256) backsolve_leaf_kernel(DevSymbolic S, const LeafRec* recs, int count,
-                                                             const double* arena, double* delta, DevStatus* status) {
+__device__ __forceinline__ void backsolve_leaf_wave(const DevSymbolic& S, const LeafRec* recs, int count, int k,
+                                                    const double* arena, double* delta, DevStatus* status) {
   const int lane = threadIdx.x & 63;
-  const int k = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (k >= count) return;
   const LeafRec rec = recs[k];
   if (wildfire_skip(S, rec.front, lane == 0)) return;  // a clique no change reaches
@@ -3714,14 +3716,131 @@ __global__ void __launch_bounds__(256) backsolve_leaf_kernel(DevSymbolic S, cons
     if (!isfinite(mine)) atomicAdd(&status->n_nonfinite, 1);
   }
 }
+// SEVERAL cliques to a wave: G = 16 or 32 lanes a clique, for the cliques whose separator has at most R G rows (R =
+// kLeafPackRows register rows a lane; the host's rule: leaf_pack_class).  Lane l' of a group holds rows F + l' + j G,
+// j < R; everything else is the wave form above on the group's own lanes.  The bits are those of the wave form.  There
+// lane l accumulates rows F + l and F + l + 64 (fma, in that order) and the xor tree runs over 32, 16, ... 1.  Row
+// F + l' + j G is a row of the wave form's lane l = (l' + j G) % 64, so lane l' keeps one accumulator for each of the
+// 64 / G lanes l', l' + G, ... it stands for, fills accumulator j % (64 / G) with row j in ascending j (the wave form's
+// order within a lane), and adds the accumulators pairwise the way the xor steps over 32 ... G pair those lanes: with
+// G = 32 acc0 + acc1, with G = 16 (acc0 + acc2) + (acc1 + acc3).  A class whose separators end before row F + 64 has no
+// second row in any of those lanes: the wave form's second fma is fma(0, 0, v) = v + 0 there, which is kept as `+ 0` (it
+// turns a -0 into +0), and a lane past the separator holds +0.  The tree then runs over G / 2 ... 1 inside the group,
+// and the triangle and the right-hand side come from the group's lanes (a shuffle where the wave form reads a lane).
+// A group whose clique is skipped (past the end, or clean in a wildfire pass) leaves; no lane of another group reads it.
+template <int FM, int G>
+__device__ __forceinline__ void backsolve_leaf_packed(const DevSymbolic& S, const LeafRec* recs, int count, int k0,
+                                                      const double* arena, double* delta, DevStatus* status) {
+  static_assert(FM <= 8 && (G == 16 || G == 32), "the triangle travels in F * F <= G lanes");
+  const int lane = threadIdx.x & 63, lp = lane & (G - 1), base = lane - lp;
+  const int k = k0 + lane / G;
+  if (k >= count) return;
+  const LeafRec* rec = recs + k;
+  if (wildfire_skip(S, rec->front, lp == 0)) return;  // a clique no change reaches
+  const int n = rec->n, F = rec->F;
+  const double* A = arena + rec->off;
+  const int* gi = S.gidx + rec->gidx_ptr;
+  constexpr int R = kLeafPackRows, NA = 64 / G;   // register rows a lane; the lanes of the wave form a lane stands for
+  int g[R];
+  double a[R][FM];
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const int r = F + lp + G * j;
+    const bool ok = r < n - 1;
+    g[j] = ok ? gi[r] : -1;
+#pragma unroll
+    for (int c = 0; c < FM; ++c) a[j][c] = (ok && c < F) ? A[r + (i64)c * n] : 0.0;
+  }
+  const int gf = lp < F ? gi[lp] : -1;
+  const int tr = lp % max(F, 1), tc = lp / max(F, 1);
+  const double tri = tc < F ? A[tr + (i64)tc * n] : 0.0;
+  const double dl = lp < F ? A[(n - 1) + (i64)lp * n] : 0.0;
+  double x[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) x[j] = g[j] >= 0 ? delta[g[j]] : 0.0;
+  double yc[FM];
+#pragma unroll
+  for (int c = 0; c < FM; ++c) {
+    double acc[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) acc[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) acc[j % NA] = fma(a[j][c], x[j], acc[j % NA]);
+    if (R <= NA) {   // no row F + l + 64 in this class: the wave form's second fma, of zeros
+#pragma unroll
+      for (int i = 0; i < NA; ++i) acc[i] += 0.0;
+    }
+#pragma unroll
+    for (int h = NA / 2; h > 0; h >>= 1)   // the xor steps over 32 ... G
+#pragma unroll
+      for (int i = 0; i < h; ++i) acc[i] += acc[i + h];
+    yc[c] = acc[0];
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) yc[c] += __shfl_xor(yc[c], o, 64);
+    yc[c] = __shfl(dl, base + c, 64) - yc[c];
+  }
+  // L11' x = y, backwards (every lane of the group computes the same values)
+  double xv[FM];
+#pragma unroll
+  for (int c = FM - 1; c >= 0; --c) {
+    xv[c] = 0.0;
+    const double tcc = __shfl(tri, base + min(c + c * F, G - 1), 64);
+    double acc = yc[c];
+#pragma unroll
+    for (int r = c + 1; r < FM; ++r) {
+      const double trc = __shfl(tri, base + min(r + c * F, G - 1), 64);
+      if (r < F) acc -= trc * xv[r];
+    }
+    if (c < F) xv[c] = acc / tcc;
+  }
+  double mine = 0.0;
+#pragma unroll
+  for (int c = 0; c < FM; ++c) mine = (lp == c) ? xv[c] : mine;
+  if (lp < F) {
+    delta[gf] = mine;
+    if (!isfinite(mine)) atomicAdd(&status->n_nonfinite, 1);
+  }
+}
 
-void launch_backsolve_leaf(const DevSymbolic& S, const LeafRec* recs, int count, int max_F, const double* arena,
-                           double* delta, DevStatus* status, hipStream_t st) {
-  if (!count) return;
-  const int grid = (count + 3) / 4;
-  if (max_F <= 4) backsolve_leaf_kernel<4><<<grid, 256, 0, st>>>(S, recs, count, arena, delta, status);
-  else if (max_F <= 8) backsolve_leaf_kernel<8><<<grid, 256, 0, st>>>(S, recs, count, arena, delta, status);
-  else backsolve_leaf_kernel<kLeafMaxF><<<grid, 256, 0, st>>>(S, recs, count, arena, delta, status);
+// One launch for the level's leaf cliques: the workgroups of the 16-lane class first, then the 32-lane class, then the
+// wave form (four waves a workgroup in each; recs is partitioned the same way, kernels.h: LeafPack).
+template <int FM>
+__global__ void __launch_bounds__(256) backsolve_leaf_kernel(DevSymbolic S, const LeafRec* recs, LeafPack pk,
+                                                             const double* arena, double* delta, DevStatus* status) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int b = blockIdx.x;
+  if constexpr (FM <= 8) {
+    if (b < pk.nb16) {
+      backsolve_leaf_packed<FM, 16>(S, recs, pk.n16, (b * 4 + wave) * 4, arena, delta, status);
+      return;
+    }
+    b -= pk.nb16;
+    if (b < pk.nb32) {
+      backsolve_leaf_packed<FM, 32>(S, recs + pk.n16, pk.n32, (b * 4 + wave) * 2, arena, delta, status);
+      return;
+    }
+    b -= pk.nb32;
+    recs += pk.n16 + pk.n32;
+  }
+  backsolve_leaf_wave<FM>(S, recs, pk.n64, b * 4 + wave, arena, delta, status);
+}
+
+int leaf_pack_class(int n, int F, int max_F) {
+  const int sep = n - 1 - F;
+  if (max_F > 8) return 64;   // (the widest instantiation has the wave form only)
+  if (sep <= 16 * kLeafPackRows && F * F <= 16) return 16;
+  if (sep <= 32 * kLeafPackRows && F * F <= 32) return 32;
+  return 64;
+}
+
+void launch_backsolve_leaf(const DevSymbolic& S, const LeafRec* recs, int n16, int n32, int n64, int max_F,
+                           const double* arena, double* delta, DevStatus* status, hipStream_t st) {
+  if (n16 + n32 + n64 == 0) return;
+  const LeafPack pk{n16, n32, n64, (n16 + 15) / 16, (n32 + 7) / 8};
+  const int grid = pk.nb16 + pk.nb32 + (n64 + 3) / 4;
+  if (max_F <= 4) backsolve_leaf_kernel<4><<<grid, 256, 0, st>>>(S, recs, pk, arena, delta, status);
+  else if (max_F <= 8) backsolve_leaf_kernel<8><<<grid, 256, 0, st>>>(S, recs, pk, arena, delta, status);
+  else backsolve_leaf_kernel<kLeafMaxF><<<grid, 256, 0, st>>>(S, recs, pk, arena, delta, status);
 }
 
 // ---------------------------------------------------------------------------------------------

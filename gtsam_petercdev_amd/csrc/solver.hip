@@ -339,6 +339,19 @@ static void dev_factorize(gsx_context* c, double lambda) {
   timer_end(c, PH_FACTORIZE);
 }
 
+// All leaf-kernel cliques of a level in one launch: from the partitioned copy where narrow cliques share a wave
+// (handle.h: d_leaf_bs_recs — the leaf cliques are childless, all of level 0), else a wave each in schedule order.
+static void backsolve_leaves(gsx_context* c, int l) {
+  const Symbolic& S = c->S;
+  const int n = S.lvl_leaf_end[l] - S.lvl_ptr[l];
+  if (l == 0 && c->leaf_bs_n[0] + c->leaf_bs_n[1] > 0)
+    launch_backsolve_leaf(c->DS, c->d_leaf_bs_recs.p, c->leaf_bs_n[0], c->leaf_bs_n[1], c->leaf_bs_n[2], c->leaf_max_F[0],
+                          c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
+  else
+    launch_backsolve_leaf(c->DS, c->d_leaf_recs.p + (S.lvl_ptr[l] - c->leaf_base), 0, 0, n, c->leaf_max_F[l], c->d_arena.p,
+                          c->d_delta.p, c->d_status.p, c->stream);
+}
+
 // The level-by-level back-substitution over ALL fronts.  wf: ISAM2's partial back-substitution — the kernels skip the
 // cliques no change reaches (DS.wf_*), and a bookkeeping pass follows every level (nullptr: all cliques).
 static void dev_backsolve_levels(gsx_context* c, const WildfireArgs* wf) {
@@ -406,10 +419,9 @@ static void dev_backsolve_levels(gsx_context* c, const WildfireArgs* wf) {
         if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
       }
     }
-    // all leaf-kernel cliques of the level in one launch (a wave each)
+    // all leaf-kernel cliques of the level in one launch
     if (S.lvl_leaf_end[l] > S.lvl_ptr[l])
-      launch_backsolve_leaf(c->DS, c->d_leaf_recs.p + (S.lvl_ptr[l] - c->leaf_base), S.lvl_leaf_end[l] - S.lvl_ptr[l],
-                            c->leaf_max_F[l], c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
+      backsolve_leaves(c, l);
     if (wf) {  // the leaf cliques (F <= 16) a thread each, the others a wave each
       launch_wildfire_post(c->DS, c->d_sched.p + S.lvl_ptr[l], le - S.lvl_ptr[l], false, *wf, c->d_delta.p, c->stream);
       launch_wildfire_post(c->DS, c->d_sched.p + le, n_rest, true, *wf, c->d_delta.p, c->stream);
@@ -478,10 +490,9 @@ void dev_backsolve(gsx_context* c, const WildfireArgs* wf) {
     if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
     debug_sync(c, "backsolve_tree", c->bst_roots, c->bst_total);
   }
-  // all leaf-kernel cliques (childless: level 0) in one launch, a wave each
+  // all leaf-kernel cliques (childless: level 0) in one launch
   if (S.n_levels > 0 && S.lvl_leaf_end[0] > S.lvl_ptr[0])
-    launch_backsolve_leaf(c->DS, c->d_leaf_recs.p + (S.lvl_ptr[0] - c->leaf_base), S.lvl_leaf_end[0] - S.lvl_ptr[0],
-                          c->leaf_max_F[0], c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
+    backsolve_leaves(c, 0);
   timer_end(c, PH_BACKSOLVE);
 }
 
@@ -720,6 +731,8 @@ gsx_status gsx_create(const gsx_problem_desc* desc, int32_t device, gsx_handle* 
   {
     const char* e = std::getenv("GSX_FUSED_STAR");
     c->fused_star_env = !(e && std::atoi(e) == 0);
+    e = std::getenv("GSX_BS_LEAF_PACK");
+    c->bs_leaf_pack_env = !(e && std::atoi(e) == 0);
   }
   int n = 0;
   if (hipGetDeviceCount(&n) == hipSuccess && n > 0 && device >= 0 && device < n && hipSetDevice(device) == hipSuccess &&

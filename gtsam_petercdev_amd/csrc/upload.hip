@@ -338,6 +338,21 @@ gsx_status upload_symbolic(gsx_context* c) {
     c->leaf_base = b;
     c->h_leaf_recs = lr;
     HIPCHK(c, c->d_leaf_recs.upload(lr, st));
+    // the back-substitution's copy: a stable partition by lanes per clique (kernels.h: leaf_pack_class), made only when
+    // some clique shares its wave
+    int max_F = 0, cnt[3] = {0, 0, 0};
+    auto cls = [&](const LeafRec& r) { const int g = leaf_pack_class(r.n, r.F, max_F); return g == 16 ? 0 : g == 32 ? 1 : 2; };
+    for (const LeafRec& r : lr) max_F = std::max(max_F, r.F);
+    if (c->bs_leaf_pack_env)
+      for (const LeafRec& r : lr) ++cnt[cls(r)];
+    c->leaf_bs_n[0] = c->leaf_bs_n[1] = c->leaf_bs_n[2] = 0;
+    if (cnt[0] + cnt[1] > 0) {
+      std::vector<LeafRec> br(lr.size());
+      size_t at[3] = {0, (size_t)cnt[0], (size_t)cnt[0] + cnt[1]};
+      for (const LeafRec& r : lr) br[at[cls(r)]++] = r;
+      for (int q = 0; q < 3; ++q) c->leaf_bs_n[q] = cnt[q];
+      HIPCHK(c, c->d_leaf_bs_recs.upload(br, st));
+    }
   }
   HIPCHK(c, c->d_H.alloc(std::max<int64_t>(S.h_size, 1)));
   HIPCHK(c, c->d_arena.alloc(std::max<int64_t>(S.arena_size, 1)));
