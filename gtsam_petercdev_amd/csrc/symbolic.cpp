@@ -509,13 +509,14 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
     // Symbolic pass, children before parents.  A row is a set of variables; in a front the frontal variables are taken
     // in order: of the rows that hold the variable, as many as it has scalars become pivots (generic rank), the others
     // take the union of those rows' variables without it.  What is left goes — all rows of the front together, each with
-    // the union of their variables — to the front where the first of those variables is frontal: an ancestor whose front
-    // holds all of them (they are a clique of the filled graph), possibly far up; the fronts in between never see the rows
-    // (Constrained::QR leaves a row without an entry in the column alone, NoiseModel.cpp:566-590).
+    // ITS OWN variables — to the front where the first variable of any of them is frontal: an ancestor whose front holds
+    // all of them (they are a clique of the filled graph), possibly far up; the fronts in between never see the rows
+    // (Constrained::QR leaves a row without an entry in the column alone, NoiseModel.cpp:566-590).  A row that holds none
+    // of that front's frontal variables (two leftover rows of one front need not share a variable) finds no pivot
+    // there, is counted among that front's leftovers and rides on with them until it reaches its own first variable.
     struct Arrival {
-      int src;                 // constrained-front index of the sender
-      int rows;
-      std::vector<int> vars;   // sorted by position
+      int src;                              // constrained-front index of the sender
+      std::vector<std::vector<int>> rows;   // per leftover row: its variables, sorted by position
     };
     std::vector<std::vector<Arrival>> arrive(nfr);
     std::vector<int> loc(n, -1);
@@ -529,7 +530,7 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
         rows.push_back(std::move(vs));
       }
       for (const Arrival& a : arrive[f])
-        for (int r = 0; r < a.rows; ++r) rows.push_back(a.vars);
+        for (const std::vector<int>& vs : a.rows) rows.push_back(vs);
       const int in = (int)rows.size();
       if (in > 1024) {
         err = "more than 1024 hard-constraint rows meet in one clique";
@@ -555,21 +556,25 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
           else rows[touching[q]] = uni;
         }
       }
-      int fwd = 0;
-      std::vector<int> uni;
+      std::vector<std::vector<int>> left;   // the leftover rows, each with its own variables
+      std::vector<int> uni;                 // ... and the union of those: what con_fwd_map must cover
       for (int r = 0; r < in; ++r) {
         if (used[r] || rows[r].empty()) continue;   // (an empty row says 0 = d: nothing left to enforce)
-        ++fwd;
+        left.push_back(rows[r]);
         std::vector<int> tmp;
         std::set_union(uni.begin(), uni.end(), rows[r].begin(), rows[r].end(), std::back_inserter(tmp), by_pos);
         uni.swap(tmp);
       }
+      const int fwd = (int)left.size();
       const int me = (int)S.con_fronts.size();
       S.con[f] = 1;
       S.con_index[f] = me;
       S.con_fronts.push_back(f);
       S.con_in.push_back(in);
       S.con_fwd.push_back(fwd);
+      if (std::getenv("GSX_CON_TRACE"))
+        fprintf(stderr, "[constraints] front %d: %d rows in (%d its own), at most %d handed on\n", f, in,
+                (int)own[f].size(), fwd);
       int o = 0;
       for (int k = S.fvar_ptr[f]; k < S.fvar_ptr[f + 1]; ++k) {
         loc[S.fvars[k]] = o;
@@ -591,7 +596,7 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
       S.con_fwd_map_ptr.push_back((int)S.con_fwd_map.size());
       if (fwd > 0) {
         const int dest = S.front_of_var[uni.front()];
-        arrive[dest].push_back(Arrival{me, fwd, uni});
+        arrive[dest].push_back(Arrival{me, std::move(left)});
         std::vector<int> dloc(0);
         int od = 0;
         std::vector<std::pair<int, int>> dvars;   // (variable, offset) of the destination front

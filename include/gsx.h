@@ -238,9 +238,16 @@ enum {
  *   - gsx_get_conditional of a clique with constraint pivots gives an EQUIVALENT conditional (a pivot row has unit
  *     diagonal and comes first in its clique's elimination), not the reference's row for row;
  *   - NOT available on such a problem: marginal covariances and Dogleg (GSX_E_STATE), sharding (gsx_set_ordering fails);
- *   - a constraint row whose entries in its clique's frontal variables all vanish NUMERICALLY although its factor
- *     holds them (a rank-deficient constraint Jacobian) is reported as GSX_E_INDETERMINATE by the solve — the reference
- *     passes such a row on to the parent clique. */
+ *   - a clique that takes in more constraint rows than it has frontal scalars hands the others on, each with the
+ *     variables it still holds, to the clique where the first of them is frontal; rows of one clique with DIFFERENT
+ *     supports (excess rows on (a, x) and on (b, y) of a clique {a, b}) are handed on too, each until it reaches its
+ *     own first variable.  How many rows a clique may hand on is planned from the variables the factors hold, assuming
+ *     that r rows holding a variable of d scalars give min(r, d) pivots;
+ *   - what is refused: a constraint row that leaves FEWER pivots than that plan — its entries in its clique's frontal
+ *     variables all vanish NUMERICALLY although its factor holds them, or rows that are dependent within a variable's
+ *     columns (a rank-deficient constraint Jacobian) — and still says something about the separator is reported as
+ *     GSX_E_INDETERMINATE by the solve; the reference passes such a row on to the parent clique.  A row that reduces
+ *     to 0 = d (redundant or inconsistent, nothing left in any column) is dropped, as the reference drops it. */
 
 /* ---- ordering kinds for gsx_compute_ordering ----------------------------- */
 enum {
