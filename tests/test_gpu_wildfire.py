@@ -4,7 +4,9 @@ gsx_backsubstitute_wildfire) against a literal restatement of the reference's tr
 optimizeWildfireNode / optimizeWildfireNonRecursive; gtsam/nonlinear/ISAM2-impl.cpp:48-77) run in numpy on the ORACLE's
 Bayes tree and its [R S d] conditionals at the same values.  The reference holds no known answers for the traversal
 (its ISAM2 tests compare against batch solutions), so the expected numbers come from the restatement: parity of the
-traversal itself is pinned by construction (same conditionals, same rule), not by a reference fixture."""
+traversal itself is pinned by construction (same conditionals, same rule), not by a reference fixture.
+These are whole workloads under a norm bound; the judging per clique outcome (skipped / restored / kept) and per kernel
+of the level schedule, bit for bit and at backward-error bounds, lives in tests/test_gpu_wildfire_classes.py."""
 import numpy as np
 import pytest
 
