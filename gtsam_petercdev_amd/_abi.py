@@ -28,6 +28,9 @@ NOISE_ROBUST_HUBER, NOISE_ROBUST_TUKEY, NOISE_ROBUST_CAUCHY, NOISE_BASE_MASK = 1
 ORDER_NATURAL, ORDER_MINDEGREE, ORDER_ND, ORDER_SCHUR, ORDER_SCHUR_ND = range(5)
 PRECOND_DUMMY, PRECOND_BLOCK_JACOBI = range(2)
 SOLVER_MULTIFRONTAL, SOLVER_PCG = range(2)
+# columns of gsx_get_gather_plan's segment and combine records
+GATHER_SEGMENT_FIELDS = ("group", "task", "front", "var_row", "var_col", "dB", "dA", "diag", "slot", "src_begin", "src_end")
+GATHER_COMBINE_FIELDS = ("group", "task", "slot0", "nslots")
 
 STATE_DIM = {VAR_POSE2: 3, VAR_POSE3: 12, VAR_CAMERA: 17}
 TANGENT_DIM = {VAR_POSE2: 3, VAR_POSE3: 6, VAR_CAMERA: 9}

@@ -94,6 +94,24 @@ class ProductBackend(A.Backend):
         self._check(self._fn("get_front_classes")(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "get_front_classes")
         return out[:n.value]
 
+    def gather_plan(self) -> dict:
+        """gsx_get_gather_plan: the extend-add plan into the blocked fronts.  "segments": one dict per segment in launch
+        order (A.GATHER_SEGMENT_FIELDS; group -1 = the side group, var_row -1 = the right-hand side), "sources":
+        [(child front, F of a lean leaf or 0 for a stored block)], "combines": one dict per multi-segment task
+        (A.GATHER_COMBINE_FIELDS)."""
+        ns, nsrc, nm = C.c_int32(), C.c_int64(), C.c_int32()
+        fn = self._fn("get_gather_plan")
+        self._check(fn(self._h, C.byref(ns), C.byref(nsrc), C.byref(nm), None, None, None), "get_gather_plan")
+        seg = np.zeros((max(ns.value, 1), len(A.GATHER_SEGMENT_FIELDS)), np.int64)
+        src = np.zeros((max(nsrc.value, 1), 2), np.int32)
+        comb = np.zeros((max(nm.value, 1), len(A.GATHER_COMBINE_FIELDS)), np.int32)
+        self._check(fn(self._h, None, None, None, seg.ctypes.data_as(C.POINTER(C.c_int64)),
+                       src.ctypes.data_as(C.POINTER(C.c_int32)), comb.ctypes.data_as(C.POINTER(C.c_int32))),
+                    "get_gather_plan")
+        return {"segments": [dict(zip(A.GATHER_SEGMENT_FIELDS, (int(v) for v in row))) for row in seg[:ns.value]],
+                "sources": [(int(c), int(f)) for c, f in src[:nsrc.value]],
+                "combines": [dict(zip(A.GATHER_COMBINE_FIELDS, (int(v) for v in row))) for row in comb[:nm.value]]}
+
     def shard_probe_buffer(self):
         """(device address, doubles) of a buffer the library hipMalloc'd itself and that holds nothing between calls — what
         distributed.checked_allreduce probes the in-place collective on (gsx_scratch_buffer)."""

@@ -3304,8 +3304,8 @@ void launch_front_star_leaf(const DevSymbolic& S, const StarLeafRec* recs, int c
 // ---------------------------------------------------------------------------------------------
 // big_gather: deterministic extend-add into big parents.  A task = one destination block (a pair of
 // parent variables) with the list, in child order, of the matching blocks of the children's Schur
-// complements (built once by the symbolic analysis).  Lists are cut into segments of <= 96 sources,
-// one wave each (two block entries per lane, four loads in flight).  A single-segment task adds its
+// complements (built once by the symbolic analysis).  Lists are cut into segments of <= 64 sources
+// (kGatherChunk), one wave each, one source record per lane.  A single-segment task adds its
 // sum straight into the pre-initialised front; a multi-segment task parks partial sums in scratch
 // slots that the combine pass adds in slot order.  No atomics: bitwise reproducible.
 // (HessianFactor::updateHessian of the children's remaining factors,

@@ -879,6 +879,63 @@ gsx_status gsx_get_front_classes(gsx_handle h, int32_t* classes) {
   return GSX_OK;
 }
 
+gsx_status gsx_get_gather_plan(gsx_handle h, int32_t* n_segments, int64_t* n_sources, int32_t* n_combines, int64_t* segments,
+                               int32_t* sources, int32_t* combines) {
+  if (!h) return GSX_E_INVALID;
+  if (!h->has_symbolic) return GSX_E_STATE;
+  const Symbolic& S = h->S;
+  const int nseg = (int)S.gseg_task.size(), nm = (int)S.gm_task.size();
+  if (n_segments) *n_segments = nseg;
+  if (n_sources) *n_sources = (int64_t)S.gs_child.size();
+  if (n_combines) *n_combines = nm;
+  // (the side group is the last gather group, index n_ulevels: reported as -1)
+  auto group_of = [&](const std::vector<int>& ptr, int i) {
+    int l = 0;
+    while (l < S.n_ulevels && i >= ptr[l + 1]) ++l;
+    return l == S.n_ulevels ? -1 : l;
+  };
+  if (segments)
+    for (int i = 0; i < nseg; ++i) {
+      const int t = S.gseg_task[i], p = S.gt_front[t], dims = S.gt_dims[t];
+      // the block's two parent variables, back from its arena offset: row r, column c of the front
+      const int64_t rel = S.gt_dst[t] - S.off[p];
+      const int rc[2] = {(int)(rel % S.N[p]), (int)(rel / S.N[p])};
+      int var[2] = {-1, -1};   // -1: the right-hand side (row N - 1)
+      for (int q = 0; q < 2; ++q) {
+        int o = 0;
+        for (int k = S.fvar_ptr[p]; k < S.fvar_ptr[p + 1] && var[q] < 0; ++k) {
+          if (o == rc[q]) var[q] = S.fvars[k];
+          o += h->P.dims[S.fvars[k]];
+        }
+      }
+      int64_t* o = segments + (int64_t)i * 11;
+      o[0] = group_of(S.gseg_lvl_ptr, i);
+      o[1] = t;
+      o[2] = p;
+      o[3] = var[0];
+      o[4] = var[1];
+      o[5] = dims & 255;
+      o[6] = (dims >> 8) & 255;
+      o[7] = dims >> 16;
+      o[8] = S.gseg_slot[i];
+      o[9] = S.gseg_begin[i];
+      o[10] = S.gseg_end[i];
+    }
+  if (sources)
+    for (size_t i = 0; i < S.gs_child.size(); ++i) {
+      sources[2 * i] = S.gs_child[i];
+      sources[2 * i + 1] = S.gs_loc2[i] >= 0 ? S.F[S.gs_child[i]] : 0;
+    }
+  if (combines)
+    for (int i = 0; i < nm; ++i) {
+      combines[4 * i] = group_of(S.gm_lvl_ptr, i);
+      combines[4 * i + 1] = S.gm_task[i];
+      combines[4 * i + 2] = S.gm_slot[i];
+      combines[4 * i + 3] = S.gm_nslots[i];
+    }
+  return GSX_OK;
+}
+
 gsx_status gsx_scratch_buffer(gsx_handle h, double** device_ptr, int64_t* count) {
   if (!h || !device_ptr || !count) return GSX_E_INVALID;
   gsx_status st = need_device(h);

@@ -998,7 +998,10 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
           }
         }
     // (worth a second queue only when it moves real work: a tenth of the lean leaves, and thousands of them)
-    if (n_side >= 4096 && n_side * 10 >= n_lean) S.side_level0 = l0;
+    // (GSX_SIDE_MIN lowers the count for experiments and for tests that reach the side group on a small graph)
+    int64_t side_min = 4096;
+    if (const char* e = std::getenv("GSX_SIDE_MIN")) side_min = std::max(1, std::atoi(e));
+    if (n_side >= side_min && n_side * 10 >= n_lean) S.side_level0 = l0;
     else std::fill(S.side.begin(), S.side.end(), 0);
   }
   // ---- schedule: by level; inside a level: leaf-kernel fronts, other small (LDS) fronts by N, big fronts ----

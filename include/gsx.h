@@ -468,6 +468,20 @@ gsx_status gsx_scratch_buffer(gsx_handle h, double** device_ptr, int64_t* count)
  * 2 blocked path in HBM, 3 medium (frontal panel in LDS, trailing block in HBM); bit 2 = tree front (dependency-driven
  * launch); bit 3 = lean leaf (no Schur complement stored: its blocked parent's gather forms it) */
 gsx_status gsx_get_front_classes(gsx_handle h, int32_t* classes);
+/* The extend-add plan of the current tree, read-only (host side; answers on a handle without a device): how the
+ * contributions of the children reach the blocked fronts.  A segment is one wave's work: up to 64 consecutive sources
+ * of one destination block.  Pass NULL arrays to query the counts, then fill:
+ *   segments[11 * i ..]  group (the upper level whose launch runs it, -1: the side group of lean leaves), task (one per
+ *                        destination block and group), destination front, variable of the block's rows (-1: the
+ *                        right-hand side), variable of its columns (indices as in gsx_get_tree), rows dB, columns dA,
+ *                        1 for a diagonal block, scratch slot (-1: the sum is added straight into the front), first
+ *                        source, one past the last source
+ *   sources[2 * s ..]    child front, and F > 0 for a lean leaf (the product form of its n x F panel) or 0 for a stored
+ *                        Schur-complement block
+ *   combines[4 * m ..]   group, task, first scratch slot, number of slots: the tasks of more than one segment, whose
+ *                        partial sums the combine pass adds in slot order */
+gsx_status gsx_get_gather_plan(gsx_handle h, int32_t* n_segments, int64_t* n_sources, int32_t* n_combines,
+                               int64_t* segments, int32_t* sources, int32_t* combines);
 gsx_status gsx_get_ordering(gsx_handle h, uint64_t* keys_out);
 /* Bayes-tree structure for parity checks: per front the frontal / separator
  * variable indices (CSR) and the parent front (-1 = root).  Pass NULL arrays to
