@@ -68,6 +68,21 @@ struct BigLevel {
   int begin = 0, count = 0;
   BigPlan plan;  // rounds of the level's blocked fronts (bigfront.hip)
 };
+// One launch of the back-substitution (upload.hip: plan_backsolve makes them, solver.hip: run_bs_launch runs them).
+enum BsKind {
+  BS_BIG,      // blocked fronts whose L11 tiles fit in LDS: backsolve_big_kernel
+  BS_SMALL,    // LDS-class fronts of at most 64 frontal columns: backsolve_small_kernel, or small2 when max_F > 32
+  BS_GENERIC,  // backsolve_kernel with `threads` threads a front: what the two above refuse
+  BS_LEAF,     // all leaf-kernel cliques of the level (the handle's leaf tables say how: leaf_bs_n, leaf_max_F)
+  BS_TREE      // the tree fronts of all levels in one dependency-driven launch (the handle's bst_* tables)
+};
+struct BsLaunch {
+  BsKind kind;
+  int level;
+  int begin, count;  // range of the schedule the plan is over (S.sched or S.usched; BS_LEAF: of S.sched; BS_TREE: the number of tree fronts)
+  int max_n, max_F;  // largest rows / frontal columns in the range
+  int threads;       // BS_GENERIC: 64, 256 or 1024; the other kernels have a block size of their own (0)
+};
 
 enum Phase { PH_LINEARIZE, PH_ASSEMBLE_H, PH_FACTORIZE, PH_BACKSOLVE, PH_LINERR, PH_RETRACT, PH_ERROR,
              PH_FACTOR_SMALL, PH_FACTOR_BIG, PH_FACTOR_LEAF, PH_K_SYRK, PH_K_TRSM, PH_K_POTRF0, PH_K_GATHER,
@@ -158,6 +173,9 @@ struct Context {
     size_t med_lds;   // > 0: the tier of the medium fronts (front_tree_med_kernel), bytes of LDS
   };
   std::vector<TreeTier> tree_tiers;
+  // the back-substitution's launches (plan_backsolve).  bs_level_plan: every front level by level, top-down, over d_sched —
+  // the wildfire pass and GSX_BS_TREE_OFF.  bs_plan: the upper levels top-down over d_usched, the tree launch, the leaves.
+  std::vector<BsLaunch> bs_level_plan, bs_plan;
   DevBuf<i64> d_gt_dst;  // gather tasks / segments for big parents
   DevBuf<GatherSeg> d_gsegs;
   DevBuf<GatherSrc> d_gsrcs;
@@ -477,6 +495,7 @@ int factor_type_list(const HostProblem& P, int f);
 void whiten_linear_factor(const HostProblem& P, int f, const double* src, double* J);
 gsx_status upload_problem(gsx_context* c);
 gsx_status upload_symbolic(gsx_context* c);
+void plan_backsolve(const Symbolic& S, std::vector<BsLaunch>& level_plan, std::vector<BsLaunch>& plan);
 // solver.hip: the device pipeline (all asynchronous up to readback) ...
 void launch_lds_group(const DevProblem& P, const DevSymbolic& S, const int* ids, const SmallLaunch& g, const double* H,
                       const double* damp, const double* scalars, double* arena, DevStatus* status, hipStream_t st);

@@ -352,84 +352,57 @@ static void backsolve_leaves(gsx_context* c, int l) {
                           c->d_delta.p, c->d_status.p, c->stream);
 }
 
+// One launch of a back-substitution plan (handle.h: BsLaunch; upload.hip: plan_backsolve); sched: the device copy of the
+// schedule the plan is over.
+static void run_bs_launch(gsx_context* c, const int* sched, const BsLaunch& b) {
+  static const char* const names[] = {"backsolve_big", "backsolve_small", "backsolve", "backsolve_leaf", "backsolve_tree"};
+  const bool timed = c->profiling > 0 && b.kind != BS_LEAF;   // (the leaf cliques' launch never had a timer of its own)
+  if (timed) timer_begin(c, PH_K_BACKSOLVE);
+  switch (b.kind) {
+    case BS_BIG:
+      launch_backsolve_big(c->DS, sched + b.begin, b.count, b.max_n, b.max_F, c->d_arena.p, c->d_delta.p, c->d_status.p,
+                           c->stream);
+      break;
+    case BS_SMALL:
+      launch_backsolve_small(c->DS, sched + b.begin, b.count, b.max_F, c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
+      break;
+    case BS_GENERIC:
+      launch_backsolve(c->DS, sched + b.begin, b.count, b.threads, b.max_n, c->d_arena.p, c->d_delta.p, c->d_status.p,
+                       c->stream);
+      break;
+    case BS_LEAF:
+      backsolve_leaves(c, b.level);
+      break;
+    case BS_TREE:
+      launch_backsolve_tree(c->DS,
+                            BacksolveTreeArgs{c->d_bst_roots.p, c->bst_roots, c->bst_total, c->d_bst_child_ptr.p,
+                                              c->d_bst_children.p, c->d_bst_ready.p, c->d_bst_counters.p,
+                                              c->d_bst_counters.p + 1, c->bst_epoch},
+                            c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
+      break;
+  }
+  if (timed) timer_end(c, PH_K_BACKSOLVE);
+  debug_sync(c, names[b.kind], b.count, b.kind == BS_GENERIC ? b.threads : b.max_n);
+}
+
 // The level-by-level back-substitution over ALL fronts.  wf: ISAM2's partial back-substitution — the kernels skip the
 // cliques no change reaches (DS.wf_*), and a bookkeeping pass follows every level (nullptr: all cliques).
 static void dev_backsolve_levels(gsx_context* c, const WildfireArgs* wf) {
   const Symbolic& S = c->S;
   timer_begin(c, PH_BACKSOLVE);
   c->delta_overwritten();  // (the callers that leave a complete undamped solution behind say so: step_solved)
+  const std::vector<BsLaunch>& plan = c->bs_level_plan;
+  size_t i = 0;
   for (int l = S.n_levels - 1; l >= 0; --l) {
-    const int se = S.lvl_small_end[l];
-    const struct {
-      int count;
-    } B{S.lvl_ptr[l + 1] - se};
-    const int le = S.lvl_leaf_end[l], n_rest = S.lvl_ptr[l + 1] - le;
-    // the blocked fronts of the level: their own kernel when L11's tiles fit in LDS (bigfront.hip)
-    int big_maxn = 0, big_maxF = 0, big_maxS = 0;
-    for (int k = se; k < S.lvl_ptr[l + 1]; ++k) {
-      big_maxn = std::max(big_maxn, S.N[S.sched[k]]);
-      big_maxF = std::max(big_maxF, S.F[S.sched[k]]);
-      big_maxS = std::max(big_maxS, S.N[S.sched[k]] - S.F[S.sched[k]]);
-    }
-    const bool big_own = B.count > 0 && backsolve_big_lds(big_maxn, big_maxF, big_maxS) > 0;
-    if (big_own) {
-      if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-      launch_backsolve_big(c->DS, c->d_sched.p + se, S.lvl_ptr[l + 1] - se, big_maxn, big_maxF, c->d_arena.p, c->d_delta.p,
-                           c->d_status.p, c->stream);
-      if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
-    }
-    // the LDS-class fronts: their own kernels when every one of them has at most 64 frontal columns
-    const int* small_ids = c->d_sched.p + le;
-    const int n_small = se - le;
-    int small_maxn = 0, small_maxF = 0;
-    for (int k = le; k < se; ++k) {
-      small_maxn = std::max(small_maxn, S.N[S.sched[k]]);
-      small_maxF = std::max(small_maxF, S.F[S.sched[k]]);
-    }
-    const bool small_own = n_small > 0 && backsolve_small_fits(small_maxn, small_maxF);
-    if (small_own) {
-      if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-      launch_backsolve_small(c->DS, small_ids, n_small, small_maxF, c->d_arena.p, c->d_delta.p, c->d_status.p,
-                             c->stream);
-      if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
-    }
-    const bool big_left = B.count > 0 && !big_own, small_left = n_small > 0 && !small_own;
-    if (big_left && small_left && n_rest <= 512 && n_rest > B.count) {
-      // few fronts: small and big ones of the level in ONE launch of the generic kernel
-      int maxn = 0;
-      for (int k = le; k < S.lvl_ptr[l + 1]; ++k) maxn = std::max(maxn, S.N[S.sched[k]]);
-      if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-      launch_backsolve(c->DS, c->d_sched.p + le, n_rest, 1024, maxn, c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
-      if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
-    } else {
-      if (big_left) {
-        int maxn = 0;
-        for (int k = se; k < S.lvl_ptr[l + 1]; ++k) maxn = std::max(maxn, S.N[S.sched[k]]);
-        if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-        launch_backsolve(c->DS, c->d_sched.p + se, S.lvl_ptr[l + 1] - se, 1024, maxn, c->d_arena.p, c->d_delta.p,
-                         c->d_status.p, c->stream);
-        if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
-      }
-      if (small_left) {
-        // the size groups of the factorization (split by LDS footprint) mean nothing here — the generic kernel keeps
-        // only n - 1 doubles per clique in LDS: all the level's LDS-class cliques go in ONE launch
-        if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-        launch_backsolve(c->DS, small_ids, n_small, small_maxn <= 48 ? 64 : 256, small_maxn, c->d_arena.p,
-                         c->d_delta.p, c->d_status.p, c->stream);
-        if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
-      }
-    }
-    // all leaf-kernel cliques of the level in one launch
-    if (S.lvl_leaf_end[l] > S.lvl_ptr[l])
-      backsolve_leaves(c, l);
+    for (; i < plan.size() && plan[i].level == l; ++i) run_bs_launch(c, c->d_sched.p, plan[i]);
     if (wf) {  // the leaf cliques (F <= 16) a thread each, the others a wave each
-      launch_wildfire_post(c->DS, c->d_sched.p + S.lvl_ptr[l], le - S.lvl_ptr[l], false, *wf, c->d_delta.p, c->stream);
-      launch_wildfire_post(c->DS, c->d_sched.p + le, n_rest, true, *wf, c->d_delta.p, c->stream);
+      const int b = S.lvl_ptr[l], le = S.lvl_leaf_end[l];
+      launch_wildfire_post(c->DS, c->d_sched.p + b, le - b, false, *wf, c->d_delta.p, c->stream);
+      launch_wildfire_post(c->DS, c->d_sched.p + le, S.lvl_ptr[l + 1] - le, true, *wf, c->d_delta.p, c->stream);
     }
   }
   timer_end(c, PH_BACKSOLVE);
 }
-
 
 // OptimizeClique top-down (gtsam/linear/linearAlgorithms-inst.h:49-117): the upper fronts level by level (Symbolic::ulevel),
 // then the tree fronts of all levels in one launch, then the leaf-kernel cliques.
@@ -439,60 +412,15 @@ void dev_backsolve(gsx_context* c, const WildfireArgs* wf) {
     dev_backsolve_levels(c, wf);
     return;
   }
-  const Symbolic& S = c->S;
   timer_begin(c, PH_BACKSOLVE);
   c->delta_overwritten();  // (the callers that leave a complete undamped solution behind say so: step_solved)
-  for (int l = S.n_ulevels - 1; l >= 0; --l) {
-    const int b0 = S.ulvl_ptr[l], se = S.ulvl_small_end[l], e = S.ulvl_ptr[l + 1];
-    // the blocked fronts of the level: their own kernel when L11's tiles fit in LDS (bigfront.hip)
-    if (e > se) {
-      int big_maxn = 0, big_maxF = 0, big_maxS = 0;
-      for (int k = se; k < e; ++k) {
-        big_maxn = std::max(big_maxn, S.N[S.usched[k]]);
-        big_maxF = std::max(big_maxF, S.F[S.usched[k]]);
-        big_maxS = std::max(big_maxS, S.N[S.usched[k]] - S.F[S.usched[k]]);
-      }
-      if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-      if (backsolve_big_lds(big_maxn, big_maxF, big_maxS) > 0)
-        launch_backsolve_big(c->DS, c->d_usched.p + se, e - se, big_maxn, big_maxF, c->d_arena.p, c->d_delta.p, c->d_status.p,
-                             c->stream);
-      else
-        launch_backsolve(c->DS, c->d_usched.p + se, e - se, 1024, big_maxn, c->d_arena.p, c->d_delta.p, c->d_status.p,
-                         c->stream);
-      if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
+  for (const BsLaunch& b : c->bs_plan) {
+    if (b.kind == BS_TREE) {   // its ticket counters start at zero, and its epoch tells this launch's entries from stale ones
+      hipMemsetAsync(c->d_bst_counters.p, 0, 2 * sizeof(int), c->stream);
+      if (++c->bst_epoch == 0) c->bst_epoch = 1;
     }
-    // the LDS-class fronts of the level that are not tree fronts (consecutive in d_usched)
-    if (se > b0) {
-      int maxn = 0, maxF = 0;
-      for (int k = b0; k < se; ++k) {
-        maxn = std::max(maxn, S.N[S.usched[k]]);
-        maxF = std::max(maxF, S.F[S.usched[k]]);
-      }
-      if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-      if (backsolve_small_fits(maxn, maxF))
-        launch_backsolve_small(c->DS, c->d_usched.p + b0, se - b0, maxF, c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
-      else
-        launch_backsolve(c->DS, c->d_usched.p + b0, se - b0, maxn <= 48 ? 64 : 256, maxn, c->d_arena.p, c->d_delta.p,
-                         c->d_status.p, c->stream);
-      if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
-    }
+    run_bs_launch(c, c->d_usched.p, b);
   }
-  if (c->bst_total > 0) {
-    // every upper front is solved: the tree fronts of all levels, one launch
-    hipMemsetAsync(c->d_bst_counters.p, 0, 2 * sizeof(int), c->stream);
-    if (++c->bst_epoch == 0) c->bst_epoch = 1;
-    if (c->profiling > 0) timer_begin(c, PH_K_BACKSOLVE);
-    launch_backsolve_tree(c->DS,
-                          BacksolveTreeArgs{c->d_bst_roots.p, c->bst_roots, c->bst_total, c->d_bst_child_ptr.p,
-                                            c->d_bst_children.p, c->d_bst_ready.p, c->d_bst_counters.p,
-                                            c->d_bst_counters.p + 1, c->bst_epoch},
-                          c->d_arena.p, c->d_delta.p, c->d_status.p, c->stream);
-    if (c->profiling > 0) timer_end(c, PH_K_BACKSOLVE);
-    debug_sync(c, "backsolve_tree", c->bst_roots, c->bst_total);
-  }
-  // all leaf-kernel cliques (childless: level 0) in one launch
-  if (S.n_levels > 0 && S.lvl_leaf_end[0] > S.lvl_ptr[0])
-    backsolve_leaves(c, 0);
   timer_end(c, PH_BACKSOLVE);
 }
 

@@ -239,6 +239,97 @@ static int small_threads_for(int n) {
   return std::min(512, t << shift);
 }
 
+// ---- the back-substitution's launch plan (handle.h: BsLaunch) -----------------------------------------------------------
+// The launches of one level's fronts above the leaf kernel: ids[sb, mid) the LDS-class ones, ids[mid, e) the blocked ones.
+// Each class has a kernel of its own that takes the class whole or not at all (backsolve_small_fits, backsolve_big_lds);
+// what they refuse goes to the generic kernel, which keeps only n - 1 doubles a front in LDS — the factorization's size
+// groups mean nothing to it, a class is ONE launch.
+// (A gap, recorded and left: launch_backsolve asks for max_n doubles of LDS against an attribute of 128 KB and nothing
+//  here refuses a front beyond that, as lds_fits does for the factorization — a front of more than 16 384 rows.)
+// level_sched: the schedule of all fronts (S.sched).  There, and only there, few generic fronts of both classes share one
+// launch, and the classes with a kernel of their own go first; the upper schedule runs the blocked fronts, then the others.
+static void plan_bs_group(const Symbolic& S, const std::vector<int>& ids, int level, int sb, int mid, int e, bool level_sched,
+                          std::vector<BsLaunch>& out) {
+  auto range = [&](int b, int end, int threads) {
+    BsLaunch r{BS_GENERIC, level, b, end - b, 0, 0, threads};
+    for (int k = b; k < end; ++k) {
+      r.max_n = std::max(r.max_n, S.N[ids[k]]);
+      r.max_F = std::max(r.max_F, S.F[ids[k]]);
+    }
+    return r;
+  };
+  BsLaunch big = range(mid, e, 1024), small = range(sb, mid, 0);
+  small.threads = small.max_n <= 48 ? 64 : 256;
+  int big_sep = 0;
+  for (int k = mid; k < e; ++k) big_sep = std::max(big_sep, S.N[ids[k]] - S.F[ids[k]]);
+  if (big.count && backsolve_big_lds(big.max_n, big.max_F, big_sep) > 0) big.kind = BS_BIG;
+  if (small.count && backsolve_small_fits(small.max_n, small.max_F)) small.kind = BS_SMALL;
+  if (big.kind != BS_GENERIC) big.threads = 0;
+  if (small.kind != BS_GENERIC) small.threads = 0;
+  const int n_rest = e - sb;
+  if (level_sched && big.count && small.count && big.kind == BS_GENERIC && small.kind == BS_GENERIC && n_rest <= 512 &&
+      n_rest > big.count) {
+    out.push_back(range(sb, e, 1024));   // few fronts: small and big ones of the level in ONE launch of the generic kernel
+    return;
+  }
+  const bool small_first = level_sched && big.kind == BS_GENERIC && small.kind == BS_SMALL;
+  const BsLaunch* order[2] = {small_first ? &small : &big, small_first ? &big : &small};
+  for (const BsLaunch* b : order)
+    if (b->count) out.push_back(*b);
+}
+
+// Both plans of a tree, from the symbolic analysis alone (no handle, no device): what every solve then only walks.
+void plan_backsolve(const Symbolic& S, std::vector<BsLaunch>& level_plan, std::vector<BsLaunch>& plan) {
+  level_plan.clear();
+  plan.clear();
+  auto leaves = [&](int l) { return BsLaunch{BS_LEAF, l, S.lvl_ptr[l], S.lvl_leaf_end[l] - S.lvl_ptr[l], 0, 0, 0}; };
+  for (int l = S.n_levels - 1; l >= 0; --l) {
+    plan_bs_group(S, S.sched, l, S.lvl_leaf_end[l], S.lvl_small_end[l], S.lvl_ptr[l + 1], true, level_plan);
+    if (leaves(l).count) level_plan.push_back(leaves(l));
+  }
+  // OptimizeClique top-down: the upper fronts level by level (Symbolic::ulevel), then — every upper front solved — the tree
+  // fronts of all levels in one launch, then the leaf-kernel cliques (childless: level 0)
+  for (int l = S.n_ulevels - 1; l >= 0; --l)
+    plan_bs_group(S, S.usched, l, S.ulvl_ptr[l], S.ulvl_small_end[l], S.ulvl_ptr[l + 1], false, plan);
+  BsLaunch tree{BS_TREE, 0, 0, 0, 0, 0, 0};
+  for (int f = 0; f < S.n_fronts; ++f)
+    if (S.tree_tier[f] >= 0) {
+      tree.count++;
+      tree.max_n = std::max(tree.max_n, S.N[f]);
+      tree.max_F = std::max(tree.max_F, S.F[f]);
+    }
+  if (tree.count) plan.push_back(tree);
+  if (S.n_levels > 0 && leaves(0).count) plan.push_back(leaves(0));
+}
+
+// (for tests/test_host_backsolve_plan.py: the plans as integers, host only; not part of the C ABI of include/gsx.h.  A
+//  handle without a device never reached upload_symbolic: it is planned here.)  which = 0: the level plan, a record
+// (front, kind, threads, max_F, launch) per front in launch order; 1: the default plan, a record (kind, level, count,
+// threads, max_n) per launch.  For a leaf-kernel clique `threads` is the lanes it is solved with: leaf_pack_class, or a wave
+// when the handle does not pack.  Returns the number of records, of which the first `cap` are written.
+extern "C" int gsxtest_backsolve_plan(gsx_context* c, int which, int* out, int cap) {
+  if (!c || !c->has_symbolic) return -1;
+  const Symbolic& S = c->S;
+  std::vector<BsLaunch> level_plan = c->bs_level_plan, plan = c->bs_plan;
+  if (!c->has_device) plan_backsolve(S, level_plan, plan);
+  std::vector<std::array<int, 5>> recs;
+  for (const BsLaunch& b : plan)
+    if (which == 1) recs.push_back({b.kind, b.level, b.count, b.threads, b.max_n});
+  for (size_t i = 0; which == 0 && i < level_plan.size(); ++i) {
+    const BsLaunch& b = level_plan[i];
+    const bool packs = b.kind == BS_LEAF && b.level == 0 && c->bs_leaf_pack_env;
+    int leaf_max_F = 0;
+    for (int k = b.begin; packs && k < b.begin + b.count; ++k) leaf_max_F = std::max(leaf_max_F, S.F[S.sched[k]]);
+    for (int k = b.begin; k < b.begin + b.count; ++k) {
+      const int f = S.sched[k];
+      const int lanes = packs ? leaf_pack_class(S.N[f], S.F[f], leaf_max_F) : 64;
+      recs.push_back({f, b.kind, b.kind == BS_LEAF ? lanes : b.threads, b.max_F, (int)i});
+    }
+  }
+  for (size_t i = 0; out && i < recs.size() && (int)i < cap; ++i) std::copy(recs[i].begin(), recs[i].end(), out + 5 * i);
+  return (int)recs.size();
+}
+
 // Build the launch plan (host) and upload the symbolic tables.
 gsx_status upload_symbolic(gsx_context* c) {
   const Symbolic& S = c->S;
@@ -625,6 +716,7 @@ gsx_status upload_symbolic(gsx_context* c) {
     B.count = (int)c->big_descs.size() - B.begin;
     plan_big_group(c->big_descs.data() + B.begin, B.count, B.plan);
   }
+  plan_backsolve(S, c->bs_level_plan, c->bs_plan);
   HIPCHK(c, c->d_usched.upload(S.usched, st));
   HIPCHK(c, c->d_rest_ids.upload(rest_ids, st));
   // ---- hard constraints: the constrained fronts by upper level, their rows and work areas ----

@@ -40,8 +40,9 @@ variables count as changed whatever they did (ISAM2Clique.cpp:237-259); the skip
 childless clique of at most 16 scalars is a leaf-kernel clique, so the leaf kernels are reached in the bottom position
 only and a middle clique is LDS-class or blocked.
 
-kernel_of() restates dev_backsolve_levels' dispatch (solver.hip) per clique from the tree, the front classes and the
-sizes.  Branches of it that no tree reaches on the level path:
+kernel_of() states the level plan of the back-substitution (upload.hip: plan_backsolve, which dev_backsolve_levels walks)
+per clique from the tree, the front classes and the sizes; test_host_backsolve_plan.py holds it to the library's own plan
+on every case here.  Branches of it that no tree reaches on the level path:
     generic backsolve_kernel with 64 threads   needs LDS-class cliques of at most 48 rows that backsolve_small_fits
                                                refuses; it refuses only F > 64 (n <= 140 holds for the class), so n > 65
     backsolve_big_kernel at F = 193            backsolve_big_lds refuses more than 192 frontal columns (kMaxChunk): F = 193
@@ -117,7 +118,7 @@ THRESHOLDS = {
 # under RELAXED amalgamation small2 keeps three storeys in its (64, 5) arms and merges the (33, 5) ones; pack16_wave6 becomes
 # two storeys of merged fronts (an A_i of at most 16 scalars joins its M_i): visited, kept or restored as a whole
 RELAXED_CASES = ["pack16_wave6", "small2"]
-# every branch of dev_backsolve_levels' dispatch that a tree can reach (module docstring: the others)
+# every branch of the level plan's dispatch (plan_backsolve) that a tree can reach (module docstring: the others)
 BRANCHES = {"leaf16", "leaf32", "leaf64", "leaf_tail", "small", "small2", "generic256", "generic1024", "combined1024", "big"}
 
 Case = namedtuple("Case", "name arr ordering s_var arms pads root position shapes")
@@ -288,9 +289,9 @@ def clique_shapes(fronts, dims):
 
 
 def kernel_of(parent, fronts, classes, dims, big_lds, packed=True):
-    """dev_backsolve_levels (solver.hip) restated: per clique the name of the kernel that back-substitutes it, from
-    gsx_get_tree's sizes and gsx_get_front_classes (bits 0-1: 0 leaf kernel, 1 LDS, 2 blocked).  big_lds(max n, max F,
-    max separator rows + 1) is bigfront.hip's backsolve_big_lds (gsxtest_backsolve_big_lds); packed = a handle made without
+    """The level plan of the back-substitution (upload.hip: plan_backsolve; compared with the library's own by
+    test_host_backsolve_plan.py): per clique the name of the kernel that back-substitutes it, from gsx_get_tree's sizes
+    and gsx_get_front_classes (bits 0-1: 0 leaf kernel, 1 LDS, 2 blocked).  big_lds(max n, max F, max separator rows + 1) is bigfront.hip's backsolve_big_lds (gsxtest_backsolve_big_lds); packed = a handle made without
     GSX_BS_LEAF_PACK=0 (kernels.hip: leaf_pack_class)."""
     shp = clique_shapes(fronts, dims)
     lvl = levels_of(parent)

@@ -22,7 +22,8 @@ longdouble restatement run on the device's own conditionals and the device's own
                after the partial call
 The margin condition (every change 100 thresholds away from its threshold) is re-asserted on the device's conditionals.
 Each case runs once more on a handle made under GSX_BS_LEAF_PACK=0: same outcomes, same counts, same words.
-Which kernel every clique ran in is restated from gsx_get_tree and gsx_get_front_classes (_wildfire_cases.kernel_of)
+Which kernel every clique ran in is stated from gsx_get_tree and gsx_get_front_classes (_wildfire_cases.kernel_of, which
+test_host_backsolve_plan.py holds to the library's own launch plan — upload.hip: plan_backsolve — clique by clique)
 and asserted; the last test asserts that every reachable branch of the dispatch saw all three outcomes (the
 unreachable ones: _wildfire_cases' docstring).  It means something only when the whole module runs in one process.
 
