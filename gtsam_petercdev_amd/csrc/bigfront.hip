@@ -5,9 +5,9 @@
 // row) is three products with very different shapes, and each gets the kernel that fits it:
 //
 //   A. big_diag   L11 = chol(A11)                one workgroup per front.  The F x F block lives in REGISTERS for the
-//                 whole factorization, as 16 x 16 tiles in the matrix-core accumulator layout spread over the
-//                 workgroup's waves; only the four current columns pass through LDS (two LDS barriers per four
-//                 pivots).  This is the only sequential chain of a front: F pivots.
+//                 whole factorization, as 16 x 16 tiles in the matrix-core accumulator layout, a tile row to a wave;
+//                 only the finished columns' strips of L pass through LDS, handed from wave to wave by flags (no
+//                 workgroup barrier).  This is the only sequential chain of a front: F pivots.
 //   B. big_rows   L21 = A21 L11^-T               one workgroup per 32 or 64 rows of A21 (and the rhs row): blocked forward
 //                 substitution along the row block, every product on the matrix cores, no inter-workgroup
 //                 dependency at all — the rows of L21 are independent of each other once L11 is known.
@@ -32,13 +32,13 @@
 
 #include "gsx_internal.h"
 #include "kernels.h"
+#include "wave_util.h"
 
 namespace gsx {
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int T = kTile;          // 32: edge of the diagonal tiles of the stored layout
-constexpr int kMaxChunk = 192;    // frontal columns one round factors (12 tile rows of 16: 78 tiles over 8 waves)
+constexpr int kMaxChunk = 192;    // frontal columns one round factors (12 tile rows of 16, a wave each)
 
 #ifdef GSX_STAMP
 __device__ unsigned long long g_rstamp[16][8];   // big_diag_rows_kernel: [wave][phase] cycles, block 0
@@ -49,356 +49,35 @@ __device__ unsigned long long g_rstamp[16][8];   // big_diag_rows_kernel: [wave]
     if (lane == 0 && blockIdx.x == 0) g_rstamp[wv][slot] += t__ - rst0__;          \
     rst0__ = t__;                                                                  \
   }
-__device__ unsigned long long g_bstamp[16];
-#define BST_BEGIN unsigned long long bst0__ = __builtin_amdgcn_s_memtime();
-#define BST_ADD(slot)                                                          \
-  {                                                                            \
-    unsigned long long t__ = __builtin_amdgcn_s_memtime();                     \
-    if (threadIdx.x == 0 && blockIdx.x == 0) g_bstamp[slot] += t__ - bst0__;   \
-    bst0__ = t__;                                                              \
-  }
 #else
-#define BST_BEGIN
-#define BST_ADD(slot)
 #define RST_BEGIN
 #define RST_ADD(slot)
 #endif
 
-__device__ __forceinline__ void lds_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 1 / sqrt(d) to full precision from the hardware seed (one cubic correction step)
-__device__ __forceinline__ double rsqrt_refined(double d) {
-  const double y0 = __builtin_amdgcn_rsq(d);
-  const double e = fma(-d * y0, y0, 1.0);
-  return fma(y0 * e, fma(e, 0.375, 0.5), y0);
-}
-
-__device__ inline void report_failure(DevStatus* status, int front) {
-  atomicAdd(&status->n_fail, 1);
-  atomicMin(&status->first_front, front);
-}
-
-// ---- A. L11 = chol(A11[c0 .. c0 + fw)) ------------------------------------------------------------------------------
-// Lower 16 x 16 tiles (ti >= tj), column-major over the triangle, tile t -> wave t % NW, slot t / NW: a wave's slots are
-// sorted by tile column and (NW >= tile rows) it owns at most one tile of any column.  A lane (li = lane & 15,
-// lk = lane >> 4) holds of a tile the entries (row 16 ti + li, column 16 tj + 4 q + lk), q = 0..3 — the accumulator
-// layout of v_mfma_f64_16x16x4 with the tile computed transposed: a rank-4 update of a tile is ONE instruction whose
-// operands are the tile column's and the tile row's L values, and a tile's own four columns ARE the row-side operand.
-// Per tile column tc (16 pivots), two workgroup barriers:
-//   D. the wave that owns the diagonal tile factors it alone, pivot by pivot, with NO cross-lane data movement but one
-//      v_readlane of the pivot: the lanes that hold column j scale it and ARE the (one non-zero k of the) operands of
-//      the rank-1 update of the tile, one matrix-core instruction.  An identity tile carried through the same column
-//      operations comes out as L_dd^-T: the inverse of the diagonal tile (published; it is also what the stored
-//      32 x 32 tile inverses are assembled from).  Chain per pivot: readlane -> rsq + correction -> mul -> mfma.
-//   O. the waves that own the other tiles of the column: L_tile = A_tile L_dd^-T, four matrix-core instructions whose
-//      row-side operand is the tile as it stands in its registers; they publish their rows of L (a 16-column strip)
-//   U. every tile to the right takes its rank-16 update, four matrix-core instructions with operands from the strip.
-//      The next diagonal tile is the first slot of its owner's chain, and that wave goes straight on to its D: the
-//      sequential part of column tc+1 runs beside the updates of column tc.
-__device__ __forceinline__ double readlane_f64(double v, int src_lane) {  // src_lane wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-  return __hiloint2double(hi, lo);
-}
-
-template <int NW, int MAXS>
-__global__ void __launch_bounds__(NW * 64) big_diag_kernel(const BigDesc* descs, int c0, int chunk, double* arena,
-                                                           DevStatus* status) {
-  constexpr int LS = 18;                 // row stride (doubles) of the L strips: operand reads hit 32 distinct bank pairs
-  __shared__ double Lc[2][kMaxChunk][LS];  // rows of L of a tile column (16 columns, tile rows below the diagonal tile), columns alternate
-  __shared__ double dinv[kMaxChunk];     // 1 / L_cc
-  __shared__ double ldiag[kMaxChunk];    // L_cc
-  __shared__ int sfail;
-  extern __shared__ double dyn[];        // the factored 32 x 32 diagonal tiles [kb][r][33], then the 16 x 16 inverses [b][i][17]
-  BST_BEGIN
-  const BigDesc d = descs[blockIdx.x];
-  const int n = d.N, F = d.F;
-  if (c0 >= F) return;
-  const int fw = min(chunk, F - c0);
-  const int nt16 = (fw + 15) >> 4, nt32 = (fw + T - 1) / T;
-  const int ntile = nt16 * (nt16 + 1) / 2;
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  double* A = arena + d.off;
-  double* X = arena + d.xoff;
-  double* tiles = dyn;
-  double* Xd = dyn + (size_t)nt32 * T * (T + 1);
-  if (tid == 0) sfail = 0;
-
-  int ti[MAXS], tj[MAXS];
-  v4d acc[MAXS];
-#pragma unroll
-  for (int s = 0; s < MAXS; ++s) {
-    const int t = wv + s * NW;
-    ti[s] = tj[s] = 0;  // an empty slot updates a tile of zeros with valid operands: harmless
-    if (t < ntile) {
-      int c = 0, rem = t;
-      while (rem >= nt16 - c) {
-        rem -= nt16 - c;
-        ++c;
-      }
-      tj[s] = c;
-      ti[s] = c + rem;
-    }
-    const int r = 16 * ti[s] + li;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int cc = 16 * tj[s] + 4 * q + lk;
-      double v = (r == cc) ? 1.0 : 0.0;  // padding beyond fw: identity (its pivots are 1, its L columns zero)
-      if (t < ntile && r < fw && cc < fw) {
-        const int hi = max(r, cc), lo = min(r, cc);  // a diagonal tile is kept symmetric (both triangles updated alike)
-        v = A[(c0 + hi) + (i64)(c0 + lo) * n];
-      }
-      acc[s][q] = v;
-    }
-  }
-
-  // rank-16 update of slot k from the strip of L
-#define GSX_UPD16(k, c)                                                           \
-  {                                                                               \
-    const double* pa = &Lc[(c)&1][16 * tj[k] + li][lk];                           \
-    const double* pb = &Lc[(c)&1][16 * ti[k] + li][lk];                           \
-    const double a0 = pa[0], a1 = pa[4], a2 = pa[8], a3 = pa[12];                 \
-    const double b0 = pb[0], b1 = pb[4], b2 = pb[8], b3 = pb[12];                 \
-    acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a0, b0, acc[k], 0, 0, 0);      \
-    acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a1, b1, acc[k], 0, 0, 0);      \
-    acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a2, b2, acc[k], 0, 0, 0);      \
-    acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a3, b3, acc[k], 0, 0, 0);      \
-  }
-  int fail = 0;
-  int defer_k = MAXS;  // first slot whose update by the PREVIOUS column is still to do (MAXS: none)
-  BST_ADD(0)
-  for (int tc = 0; tc < nt16; ++tc) {
-    const int jb = 16 * tc;
-    // this wave's tile of column tc: the column's tiles are t = start .. start + (nt16 - tc) - 1, tile row tc + (t - start)
-    const int start = tc * nt16 - tc * (tc - 1) / 2;
-    int off = (wv - start) % NW;
-    off += off < 0 ? NW : 0;
-    const bool own = off < nt16 - tc;
-    const bool diag = own && off == 0;
-    const int slot = (start + off - wv) / NW;
-    const int r = 16 * (tc + off) + li;  // this lane's row of the owned tile
-    // (the loop's back edge sits between the matrix-core updates and this read of their result: explicit wait states)
-    asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-    v4d pt = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s)
-      if (own && s == slot) pt = acc[s];
-    const int s0 = max(0, (start + (nt16 - tc) - wv + NW - 1) / NW);  // slots of tile columns <= tc: finished after this column
-    BST_ADD(1)
-
-    if (diag) {
-      // ---- D: the diagonal tile, alone.  Other waves may still be in U of the previous column on this SIMD's matrix
-      //      core: this wave is the critical path of the whole front and issues first.  The loop is straight-line code:
-      //      a branch between a matrix-core instruction and the v_readlane of its result hides the dependency from the
-      //      compiler's hazard padding (measured: stale pivots) ----
-      __builtin_amdgcn_s_setprio(3);
-      v4d E;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) E[q] = (li == 4 * q + lk) ? 1.0 : 0.0;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int q = j >> 2, lkj = j & 3;
-        __builtin_amdgcn_sched_barrier(0);  // keep the pivots apart: the chain is the schedule
-        int lj = li;
-        asm volatile("" : "+v"(lj));  // (the lane masks are two compares a pivot; hoisted out of the column loop they spill)
-        const double dj = readlane_f64(pt[q], lkj * 16 + j);
-        const double sj = rsqrt_refined(dj);  // (a non-positive pivot makes L_jj a NaN: caught when the column is stored)
-        const bool colj = lk == lkj;          // the lanes that hold column j
-        const double xj = pt[q] * sj;
-        const double xm = (colj && lj >= j) ? xj : 0.0;  // L[li][j] (zero above the diagonal)
-        const double ej = colj ? E[q] * sj : 0.0;
-        pt[q] = colj ? xm : pt[q];
-        E[q] = colj ? ej : E[q];
-        if (j < 15) {  // rank-1 update of the columns right of j: the column's lanes are the k = lkj operands, all others zero
-          const double xu = (lj > j) ? xm : 0.0;
-          pt = __builtin_amdgcn_mfma_f64_16x16x4f64(-xu, xu, pt, 0, 0, 0);
-          E = __builtin_amdgcn_mfma_f64_16x16x4f64(-xu, ej, E, 0, 0, 0);
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
-      // the diagonal of the tile: entry (li, li) sits in the lane with lk = li & 3, register li >> 2
-      if (lk == (li & 3)) {
-        const int qd = li >> 2;
-        const double l = (qd == 0) ? pt[0] : ((qd == 1) ? pt[1] : ((qd == 2) ? pt[2] : pt[3]));
-        ldiag[jb + li] = l;
-        dinv[jb + li] = 1.0 / l;
-        if (jb + li < fw && !(l > 0)) fail = 1;  // non-positive or non-finite pivot (Eigen::LLT NumericalIssue)
-      }
-      // E[row][col] = (L_dd^-1)[col][row]: published as Xd[tc][i][c] = (L_dd^-1)[i][c]; its strictly lower part inside the
-      // same 32-tile also goes to the front (transposed: the strictly upper triangle of the diagonal tile)
-      double* xd = Xd + (size_t)tc * 16 * 17;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = 4 * q + lk, c = li;
-        xd[i * 17 + c] = E[q];
-        if (i > c && jb + i < fw) A[(c0 + jb + c) + (i64)(c0 + jb + i) * n] = E[q];
-      }
-    }
-    BST_ADD(2)
-    lds_bar();
-    BST_ADD(3)
-    // the updates by the previous column that this wave put off to start its D early, beside the other waves' O
-#pragma unroll
-    for (int k = 0; k < MAXS; ++k)
-      if (k >= defer_k) GSX_UPD16(k, tc + 1)
-    defer_k = MAXS;
-    if (own && !diag) {
-      // ---- O: a tile below the diagonal tile: L_tile[row][col] = sum_k A[row][k] (L_dd^-1)[col][k] ----
-      const double* xd = Xd + (size_t)tc * 16 * 17 + li * 17 + lk;
-      v4d nt = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < 4; ++s) nt = __builtin_amdgcn_mfma_f64_16x16x4f64(xd[4 * s], pt[s], nt, 0, 0, 0);
-      pt = nt;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Lc[tc & 1][r][4 * q + lk] = pt[q];
-    }
-    BST_ADD(4)
-    // the finished tile: L inside a diagonal 32-tile goes to the square (and to LDS for the inverse), the rest to the
-    // L-panel area
-    if (own) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int cc = jb + 4 * q + lk;
-        if (r >= fw || cc >= fw || r < cc) continue;
-        const bool same = (r >> 5) == (cc >> 5);
-        (same ? A : X)[(c0 + r) + (i64)(c0 + cc) * n] = pt[q];
-        if (same) tiles[((r >> 5) * T + (r & 31)) * (T + 1) + (cc & 31)] = pt[q];
-      }
-    }
-    BST_ADD(5)
-    lds_bar();
-    BST_ADD(6)
-    // ---- U: rank-16 update of every tile right of the column: D[col][row] -= sum_k L[col][k] L[row][k].  The wave
-    //      that owns the next diagonal tile (its first unfinished slot) updates only that one now and the rest after its D ----
-    {
-      int offn = (wv - (start + nt16 - tc)) % NW;
-      offn += offn < 0 ? NW : 0;
-      const bool next_diag = tc + 1 < nt16 && offn == 0;
-#pragma unroll
-      for (int k = 0; k < MAXS; ++k)
-        if (k >= s0 && (!next_diag || k == s0)) GSX_UPD16(k, tc)
-      if (next_diag) defer_k = s0 + 1;
-    }
-    BST_ADD(7)
-  }
-#undef GSX_UPD16
-  if (fail) sfail = 1;
-  lds_bar();
-
-  // ---- (L^-1)' of every diagonal 32-tile into its strictly upper triangle (its two 16 x 16 diagonal blocks are in place:
-  //      D), 1 / L_cc into the L-panel area ----
-  for (int c = tid; c < fw; c += NW * 64) X[(c0 + c) + (i64)(c0 + c) * n] = dinv[c];
-  // the off-diagonal block of a 32-tile: X10 = -X11 (L10 X00), one wave per tile, two products of four matrix-core
-  //    instructions; the first product's accumulator IS the second one's operand (same lane layout)
-  for (int kb = wv; kb < nt32; kb += NW) {
-    if (fw - kb * T <= 16) continue;  // a single 16-block
-    const double* L10 = tiles + ((size_t)kb * T + 16) * (T + 1);
-    const double* X00 = Xd + (size_t)(2 * kb) * 16 * 17;
-    const double* X11 = Xd + (size_t)(2 * kb + 1) * 16 * 17;
-    const int w1 = min(16, fw - kb * T - 16);
-    v4d t1 = {0.0, 0.0, 0.0, 0.0}, t2 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {  // T[i][jj] = sum_k L10[i][k] X00[k][jj]; lane: t1[q] = T[4 q + lk][li]
-      const double a = (li < w1) ? L10[li * (T + 1) + 4 * s + lk] : 0.0;
-      t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, X00[(4 * s + lk) * 17 + li], t1, 0, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)    // X10[i][jj] = -sum_k X11[i][k] T[k][jj]: operand T[4 s + lk][li] = t1[s]
-      t2 = __builtin_amdgcn_mfma_f64_16x16x4f64(-X11[li * 17 + 4 * s + lk], t1[s], t2, 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {  // (L^-1)[16 + 4 q + lk][li] -> transposed position (row li, column 16 + 4 q + lk)
-      const int i = 4 * q + lk;
-      if (i < w1) A[(c0 + kb * T + li) + (i64)(c0 + kb * T + 16 + i) * n] = t2[q];
-    }
-  }
-  BST_ADD(8)
-  if (tid == 0) {
-    int bad = sfail;
-    // conditioning test on the last two pivots (cholesky.cpp:145-158): here only for the dense entry (one clique, parent ==
-    // kStandaloneFront); the fronts of a tree are tested per reference clique by cond_check_kernel
-    if (d.parent == kStandaloneFront && c0 + fw == F) {
-      int e1, e2;
-      (void)frexp(ldiag[fw - 1], &e1);
-      if (F >= 2) {
-        const double p2 = (fw >= 2) ? ldiag[fw - 2] : A[(F - 2) + (i64)(F - 2) * n];
-        (void)frexp(p2, &e2);
-        if (!(e2 - e1 < 12)) bad = 1;
-      } else if (!(e1 > -12)) {
-        bad = 1;
-      }
-    }
-    if (bad) report_failure(status, d.front);
-  }
-}
-
-// ---- D, four pivots at a time --------------------------------------------------------------------------------------
-// The pivot-by-pivot tile factorization above issues ~38 vector instructions and two matrix-core instructions per pivot
-// (the lane masks, the reciprocal square root, two rank-1 updates), ~370 cycles on a lone wave — and that chain is the
-// critical path of every blocked front.  Here the 16 x 16 tile goes four columns at a time: the 4 x 4 diagonal block is
-// read out with ten lane reads and factored, together with its inverse, in wave-uniform registers (every lane the same
-// numbers: 4 reciprocal square roots and ~30 multiply-adds); then ONE matrix-core instruction forms the block's four
-// columns of L, X = A_b M' (M = L44^-1 sits in the sixteen lanes of the operand that face the block), and ONE applies the
-// rank-4 update to the columns to the right; the inverse tile E = L_dd^-T follows with the same two instructions.
-// pt: the tile, lane (li, lk) holds (row li, column 4 q + lk); only its lower triangle is read.  A non-positive pivot
-// turns its column into NaNs (caught by the caller's test of the diagonal).
-// MEASURED, NOT USED (compile with GSX_D_BLOCK4 to switch it in; parity-green): 125 instructions per four pivots against
-// 180, and no faster — 5 400-7 600 cycles per tile against 5 900-8 600 (tools/bigfront_bench.hip, F = 192: 51.7 us
-// against 50.0; F = 30: 15.7 against 18.0).  The twenty v_readlane of the 4 x 4 block cost ~30 cycles each, as much as
-// the matrix-core and mask instructions they replace: the chain is bound by how fast ONE wave issues instructions
-// that feed scalar registers, not by their number.
-__device__ __forceinline__ void tile_potrf16_b4(v4d& pt, v4d& E, const int li, const int lk) {
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int base = 4 * b;
-    const double d00 = readlane_f64(pt[b], base), d10 = readlane_f64(pt[b], base + 1), d20 = readlane_f64(pt[b], base + 2),
-                 d30 = readlane_f64(pt[b], base + 3), d11 = readlane_f64(pt[b], 16 + base + 1),
-                 d21 = readlane_f64(pt[b], 16 + base + 2), d31 = readlane_f64(pt[b], 16 + base + 3),
-                 d22 = readlane_f64(pt[b], 32 + base + 2), d32 = readlane_f64(pt[b], 32 + base + 3),
-                 d33 = readlane_f64(pt[b], 48 + base + 3);
-    // L44 and M = L44^-1 (r_i = 1 / l_ii)
-    const double r0 = rsqrt_refined(d00);
-    const double l10 = d10 * r0, l20 = d20 * r0, l30 = d30 * r0;
-    const double r1 = rsqrt_refined(fma(-l10, l10, d11));
-    const double l21 = fma(-l20, l10, d21) * r1, l31 = fma(-l30, l10, d31) * r1;
-    const double r2 = rsqrt_refined(fma(-l21, l21, fma(-l20, l20, d22)));
-    const double l32 = fma(-l31, l21, fma(-l30, l20, d32)) * r2;
-    const double r3 = rsqrt_refined(fma(-l32, l32, fma(-l31, l31, fma(-l30, l30, d33))));
-    const double m10 = -r1 * (l10 * r0), m21 = -r2 * (l21 * r1), m32 = -r3 * (l32 * r2);
-    const double m20 = -r2 * fma(l21, m10, l20 * r0), m31 = -r3 * fma(l32, m21, l31 * r1);
-    const double m30 = -r3 * fma(l32, m20, fma(l31, m10, l30 * r0));
-    // the operand Linv16[li][base + lk]: M[li - base][lk] on the block's rows, zero elsewhere
-    const int i = li - base;
-    const double row0 = lk == 0 ? r0 : 0.0;
-    const double row1 = lk == 0 ? m10 : (lk == 1 ? r1 : 0.0);
-    const double row2 = lk == 0 ? m20 : (lk == 1 ? m21 : (lk == 2 ? r2 : 0.0));
-    const double row3 = lk == 0 ? m30 : (lk == 1 ? m31 : (lk == 2 ? m32 : r3));
-    const double aop = i == 0 ? row0 : (i == 1 ? row1 : (i == 2 ? row2 : (i == 3 ? row3 : 0.0)));
-    const v4d z = {0.0, 0.0, 0.0, 0.0};
-    const v4d x = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, pt[b], z, 0, 0, 0);
-    const v4d eb = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, E[b], z, 0, 0, 0);
-    const bool below = li >= base + 4;
-    const double xn = x[b];
-    pt[b] = below ? xn : ((i >= 0 && lk <= i) ? xn : 0.0);   // (zero above the diagonal)
-    E[b] = eb[b];
-    if (b < 3) {
-      const double xu = below ? xn : 0.0;
-      pt = __builtin_amdgcn_mfma_f64_16x16x4f64(-xu, xu, pt, 0, 0, 0);
-      E = __builtin_amdgcn_mfma_f64_16x16x4f64(-xu, eb[b], E, 0, 0, 0);
-    }
-  }
-}
-
-// ---- A'. the same L11 = chol(A11[c0 .. c0 + fw)), ROW-OWNED and barrier-free --------------------------------------------
-// Round 3.  In the kernel above every tile column costs two workgroup barriers, and the critical path D(tc) -> O of the
-// tile under the diagonal -> U of the next diagonal tile -> D(tc + 1) crosses waves twice; measured 4.6 us per 16 pivots
-// of which the D chain is 1.5-1.9.  Here wave r owns tile ROW r (tiles (r, 0..r), in registers) and nothing is a barrier:
-//   * wave tc factors its diagonal tile (D, as above) and publishes L_dd^-T (flag);
-//   * every wave r > tc then forms its tile of the column, L(r, tc) = A(r, tc) L_dd^-T (O), publishes its 16 rows of the
-//     column's strip (a per-row flag), and updates its tiles (r, tc+1 .. r) with the strip rows of the waves above it as
-//     they appear (U);
-//   * wave tc + 1's only remaining tile is its diagonal one: O, one U, and it is in its own D — ONE cross-wave hand-off
-//     (the inverse) per 16 pivots on the critical path, no wait for anybody's trailing updates.
+// ---- A. L11 = chol(A11[c0 .. c0 + fw)), ROW-OWNED and barrier-free ------------------------------------------------------
+// Lower 16 x 16 tiles (ti >= tj); wave r owns tile ROW r (tiles (r, 0..r), NW >= tile rows), in registers for the whole
+// factorization.  A lane (li = lane & 15, lk = lane >> 4) holds of a tile the entries (row 16 ti + li, column
+// 16 tj + 4 q + lk), q = 0..3 — the accumulator layout of v_mfma_f64_16x16x4 with the tile computed transposed: a rank-4
+// update of a tile is ONE instruction whose operands are the tile column's and the tile row's L values, and a tile's own
+// four columns ARE the row-side operand.  Per tile column tc (16 pivots), with nothing a barrier:
+//   D. wave tc factors its diagonal tile alone, pivot by pivot, with NO cross-lane data movement but one v_readlane of
+//      the pivot: the lanes that hold column j scale it and ARE the (one non-zero k of the) operands of the rank-1 update
+//      of the tile, one matrix-core instruction.  An identity tile carried through the same column operations comes out
+//      as L_dd^-T: the inverse of the diagonal tile, published with a flag (it is also what the stored 32 x 32 tile
+//      inverses are assembled from).  Chain per pivot: readlane -> rsq + correction -> mul -> mfma.  The loop is
+//      straight-line code: a branch between a matrix-core instruction and the v_readlane of its result hides the
+//      dependency from the compiler's hazard padding (measured: stale pivots); the sched_barrier keeps the pivots apart
+//      (the chain is the schedule), and the lane masks are two compares a pivot (hoisted out of the loop they spill).
+//      A non-positive pivot makes L_jj a NaN: caught when the diagonal is stored.
+//   O. every wave r > tc then forms its tile of the column, L(r, tc) = A(r, tc) L_dd^-T, four matrix-core instructions
+//      whose row-side operand is the tile as it stands in its registers, and publishes its 16 rows of the column's strip
+//      (a per-row flag);
+//   U. and updates its tiles (r, tc+1 .. r), four matrix-core instructions each, with the strip rows of the waves above
+//      it as they appear.
+// Wave tc + 1's only remaining tile is its diagonal one: O, one U, and it is in its own D — ONE cross-wave hand-off (the
+// inverse) per 16 pivots on the critical path, no wait for anybody's trailing updates.  (The form this replaced spread
+// the tiles over the waves column-major and paid two workgroup barriers per tile column, its critical path crossing
+// waves twice: 4.6 us per 16 pivots, of which the D chain is 1.5-1.9 — DESIGN.md, experiments that lost.)
 // Strips live in three LDS buffers (column tc in buffer tc mod 3); a wave writes column tc only when every reader of
 // column tc - 3 has reported done.  All waits are bounded polls of LDS words written by waves of this workgroup (always
 // resident together); a poll that runs out marks the front as failed instead of hanging.
@@ -449,7 +128,7 @@ __global__ void __launch_bounds__(NW * 64) big_diag_rows_kernel(const BigDesc* d
       acc[j][q] = v;
     }
   }
-  lds_bar();   // (the flags are zero)
+  lds_barrier();   // (the flags are zero)
   RST_BEGIN
   int fail = 0;
   // bounded poll of an LDS word another wave of this workgroup will set
@@ -534,7 +213,7 @@ __global__ void __launch_bounds__(NW * 64) big_diag_rows_kernel(const BigDesc* d
         }
       }
     }
-    // ---- D: this row's diagonal tile, alone (straight-line: see big_diag_kernel) ----
+    // ---- D: this row's diagonal tile, alone (straight-line, and why: see D above the kernel) ----
     {
       const int jb = 16 * r;
       asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
@@ -547,7 +226,6 @@ __global__ void __launch_bounds__(NW * 64) big_diag_rows_kernel(const BigDesc* d
       v4d E;
 #pragma unroll
       for (int q = 0; q < 4; ++q) E[q] = (li == 4 * q + lk) ? 1.0 : 0.0;
-#ifndef GSX_D_BLOCK4   // (the four-pivots-at-a-time variant below: measured no faster, see tile_potrf16_b4)
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int q = j >> 2, lkj = j & 3;
@@ -568,9 +246,6 @@ __global__ void __launch_bounds__(NW * 64) big_diag_rows_kernel(const BigDesc* d
           E = __builtin_amdgcn_mfma_f64_16x16x4f64(-xu, ej, E, 0, 0, 0);
         }
       }
-#else
-      tile_potrf16_b4(pt, E, li, lk);
-#endif
       __builtin_amdgcn_s_setprio(0);
       double* xd = Xd + (size_t)r * 16 * 17;
 #pragma unroll
@@ -600,7 +275,7 @@ __global__ void __launch_bounds__(NW * 64) big_diag_rows_kernel(const BigDesc* d
     }
   }
   if (fail) sfail = 1;
-  lds_bar();
+  lds_barrier();
 
   // ---- (L^-1)' of every diagonal 32-tile into its strictly upper triangle, 1 / L_cc into the L-panel area ----
   for (int c = tid; c < fw; c += NW * 64) X[(c0 + c) + (i64)(c0 + c) * n] = dinv[c];
@@ -756,7 +431,7 @@ __global__ void __launch_bounds__(256 * NH) big_rows_kernel(const BigDesc* descs
         tk[k][q] = (row < hi && c < wk) ? A[(ri + row) + (i64)(c0 + k * T + c) * n] : 0.0;
       }
     }
-    lds_bar();  // (a previous row block's reads of the buffers are done)
+    lds_barrier();  // (a previous row block's reads of the buffers are done)
     if constexpr (NH == 2) stash(0, stg0);
     else stash(0, stg);
 #pragma unroll
@@ -766,7 +441,7 @@ __global__ void __launch_bounds__(256 * NH) big_rows_kernel(const BigDesc* descs
       if (k + 1 < nk) fetch(k + 1, stg);
 #pragma unroll
       for (int q = 0; q < 4; ++q) Tt[row][L.cq0 + 4 * q + L.lk] = tk[k][q];
-      lds_bar();
+      lds_barrier();
       // X[r][c] = sum_{kk <= c} T[r][kk] Linv[c][kk]: columns of the first half only need kk < 16 (wave-uniform)
       v4d x = {0.0, 0.0, 0.0, 0.0};
       {
@@ -781,7 +456,7 @@ __global__ void __launch_bounds__(256 * NH) big_rows_kernel(const BigDesc* descs
         Xt[row][cc] = x[q];
         if (row < hi && cc < wk) X[(ri + row) + (i64)(c0 + k * T + cc) * n] = x[q];
       }
-      lds_bar();
+      lds_barrier();
 #pragma unroll
       for (int k2 = k + 1; k2 < NK; ++k2) {  // T_k2[r][c] -= sum_kk X[r][kk] L[32 k2 + c][32 k + kk]
         const double* pa = buf + (size_t)(k2 - k) * TS + (L.cq0 + L.li) * (T + 2) + L.lk;
@@ -849,14 +524,8 @@ __global__ void __launch_bounds__(256) big_schur_kernel(const BigDesc* descs, in
 
 #ifdef GSX_STAMP
 void big_stamp_dump(const char* what) {
-  unsigned long long h[16];
   hipDeviceSynchronize();
-  hipMemcpyFromSymbol(h, HIP_SYMBOL(g_bstamp), sizeof(h));
-  printf("[bstamp] %s: diag prologue %llu | column setup %llu | D %llu | bar1 %llu | O %llu | store %llu | bar2 %llu | U %llu | "
-         "inverse %llu  (cycles, wave 0 of block 0)\n", what, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8]);
-
-  unsigned long long z[16] = {0};
-  hipMemcpyToSymbol(HIP_SYMBOL(g_bstamp), z, sizeof(z));
+  printf("[rstamp] %s (cycles, block 0)\n", what);
   unsigned long long rs[16][8];
   hipMemcpyFromSymbol(rs, HIP_SYMBOL(g_rstamp), sizeof(rs));
   for (int w = 0; w < 12; ++w)
@@ -896,43 +565,19 @@ void launch_big_diag(const BigDesc* descs, int count, const BigPlan& plan, int r
                      hipStream_t st) {
   if (!count) return;
   static bool attr = false;
-  const auto lds_for = [](int fw) {
-    return (size_t)(((fw + T - 1) / T) * T * (T + 1) + ((fw + 15) / 16) * 16 * 17) * sizeof(double);
-  };
-  const int kTilesLds = (int)lds_for(kMaxChunk);
-  if (!attr) {  // (static + dynamic LDS exceeds the 64 KB default)
-    hipFuncSetAttribute((const void*)big_diag_kernel<12, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, kTilesLds);
-    hipFuncSetAttribute((const void*)big_diag_kernel<12, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, kTilesLds);
-    hipFuncSetAttribute((const void*)big_diag_kernel<8, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, kTilesLds);
-    hipFuncSetAttribute((const void*)big_diag_kernel<8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kTilesLds);
-    hipFuncSetAttribute((const void*)big_diag_kernel<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kTilesLds);
+  const auto lds_for = [](int w) { return (size_t)(((w + 15) / 16) * 16 * 17 + ((w + T - 1) / T) * 16 * 17) * sizeof(double); };
+  if (!attr) {
+    hipFuncSetAttribute((const void*)big_diag_rows_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_for(kMaxChunk));
+    hipFuncSetAttribute((const void*)big_diag_rows_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_for(kMaxChunk));
+    hipFuncSetAttribute((const void*)big_diag_rows_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_for(kMaxChunk));
     attr = true;
   }
   const int c0 = round * plan.chunk, fw = plan.fw[round];
   const size_t lds = lds_for(fw);
-  const int nt16 = (fw + 15) / 16;
-  static const bool v1 = std::getenv("GSX_DIAG_V1") != nullptr;
-  if (!v1) {   // the row-owned, barrier-free kernel
-    static bool attr2 = false;
-    const auto lds2_for = [](int w) { return (size_t)(((w + 15) / 16) * 16 * 17 + ((w + T - 1) / T) * 16 * 17) * sizeof(double); };
-    if (!attr2) {
-      hipFuncSetAttribute((const void*)big_diag_rows_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2_for(kMaxChunk));
-      hipFuncSetAttribute((const void*)big_diag_rows_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2_for(kMaxChunk));
-      hipFuncSetAttribute((const void*)big_diag_rows_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2_for(kMaxChunk));
-      attr2 = true;
-    }
-    const size_t lds2 = lds2_for(fw);
-    if (nt16 <= 4) big_diag_rows_kernel<4><<<count, 256, lds2, st>>>(descs, c0, plan.chunk, arena, status);
-    else if (nt16 <= 8) big_diag_rows_kernel<8><<<count, 512, lds2, st>>>(descs, c0, plan.chunk, arena, status);
-    else big_diag_rows_kernel<12><<<count, 768, lds2, st>>>(descs, c0, plan.chunk, arena, status);
-    return;
-  }
-  // tiles: nt16 (nt16 + 1) / 2 over the waves, at least as many waves as tile rows
-  if (nt16 <= 4) big_diag_kernel<4, 3><<<count, 256, lds, st>>>(descs, c0, plan.chunk, arena, status);
-  else if (nt16 <= 6) big_diag_kernel<8, 3><<<count, 512, lds, st>>>(descs, c0, plan.chunk, arena, status);
-  else if (nt16 <= 8) big_diag_kernel<8, 5><<<count, 512, lds, st>>>(descs, c0, plan.chunk, arena, status);
-  else if (nt16 <= 10) big_diag_kernel<12, 5><<<count, 768, lds, st>>>(descs, c0, plan.chunk, arena, status);
-  else big_diag_kernel<12, 7><<<count, 768, lds, st>>>(descs, c0, plan.chunk, arena, status);
+  const int nt16 = (fw + 15) / 16;   // a wave per tile row
+  if (nt16 <= 4) big_diag_rows_kernel<4><<<count, 256, lds, st>>>(descs, c0, plan.chunk, arena, status);
+  else if (nt16 <= 8) big_diag_rows_kernel<8><<<count, 512, lds, st>>>(descs, c0, plan.chunk, arena, status);
+  else big_diag_rows_kernel<12><<<count, 768, lds, st>>>(descs, c0, plan.chunk, arena, status);
 }
 
 // The form of big_rows_kernel a launch runs in, and the dynamic LDS it asks for: a chunk of fw frontal columns over
@@ -1139,7 +784,7 @@ __global__ void __launch_bounds__(kBsThreads) backsolve_big_kernel(DevSymbolic S
       xp[tid] = acc;
       if (p * T + tid < F) xs[p * T + tid] = acc;
     }
-    lds_bar();
+    lds_barrier();
     // y_k -= L_pk' x_p for every k < p: thread c of the 32 p columns left of the block
     if (tid < p * T) {
       const int k = tid >> 5, c = tid & 31;
@@ -1155,7 +800,7 @@ __global__ void __launch_bounds__(kBsThreads) backsolve_big_kernel(DevSymbolic S
       for (int r = 0; r < T; ++r) acc = fma(a[r], b[r], acc);
       y[tid] -= acc;
     }
-    lds_bar();
+    lds_barrier();
   }
   int bad = 0;
   for (int r = tid; r < F; r += kBsThreads) {
@@ -1228,14 +873,14 @@ __device__ __forceinline__ void backsolve_small_body(const DevSymbolic& S, const
     const int e = tid + 256 * q;
     tile[e & 31][e >> 5] = tv[q];
   }
-  lds_bar();
+  lds_barrier();
   double acc = 0.0;
 #pragma unroll
   for (int k = 0; k < kSteps; ++k) acc = fma(lv[k], xs[4 * (h + 2 * k) + rq], acc);
   acc += __shfl_xor(acc, 16, 64);
   acc += __shfl_xor(acc, 32, 64);
   if (rq == 0) part[h][cg] = acc;
-  lds_bar();
+  lds_barrier();
   if (wave != 0) return;
   const int l = lane & 31;
   double lc[kBsSmallF];
@@ -1308,7 +953,7 @@ __device__ __forceinline__ void backsolve_small2_body(const DevSymbolic& S, cons
     t11[e & 31][e >> 5] = v11[q];
     t10[e & 31][e >> 5] = v10[q];
   }
-  lds_bar();
+  lds_barrier();
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     double acc = 0.0;
@@ -1318,7 +963,7 @@ __device__ __forceinline__ void backsolve_small2_body(const DevSymbolic& S, cons
     acc += __shfl_xor(acc, 32, 64);
     if (rq == 0) part[h][B * p + cl] = acc;
   }
-  lds_bar();
+  lds_barrier();
   if (wave != 0) return;
   // lane c (< 64) holds the right-hand side of column c; the two 32-pivot chains run on the lanes of their block
   const int l = lane & 31;
@@ -1377,7 +1022,7 @@ __device__ __forceinline__ void backsolve_panels_body(const DevSymbolic& S, cons
   const int tid = threadIdx.x, nt = blockDim.x;
   const int wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
   for (int r = F + tid; r < n - 1; r += nt) xs[r] = delta_load<COH>(delta + gi[r]);
-  lds_bar();
+  lds_barrier();
   const int nblk = (F + B - 1) / B;
   for (int kb = nblk - 1; kb >= 0; --kb) {
     const int c0 = kb * B, w = min(B, F - c0);
@@ -1412,7 +1057,7 @@ __device__ __forceinline__ void backsolve_panels_body(const DevSymbolic& S, cons
       const int e = tid + q * 256;
       tile[e & 31][e >> 5] = treg[q];
     }
-    lds_bar();
+    lds_barrier();
     if (wave == 0) {  // solve tile' x = y backwards; lane r holds y_r
       double yr = (lane < w) ? y[lane] : 0.0;
       for (int c = w - 1; c >= 0; --c) {
@@ -1422,7 +1067,7 @@ __device__ __forceinline__ void backsolve_panels_body(const DevSymbolic& S, cons
       }
       if (lane < w) xs[c0 + lane] = yr;
     }
-    lds_bar();
+    lds_barrier();
   }
   int bad = 0;
   for (int r = tid; r < F; r += nt) {

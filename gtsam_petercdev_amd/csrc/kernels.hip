@@ -22,6 +22,7 @@
 #include "device_geometry.h"
 #include "gsx_internal.h"
 #include "kernels.h"
+#include "wave_util.h"
 
 namespace gsx {
 using namespace gsxd;
@@ -29,29 +30,9 @@ using namespace gsxd;
 #define T kTile
 
 // ---------------------------------------------------------------------------------------------
-// helpers
+// helpers (the wave-level ones: wave_util.h)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 // total in thread 0 of the block (fixed summation order => deterministic)
-typedef double v4d __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i64 readlane_i64(i64 v, int src_lane) {  // src_lane must be wave-uniform
-  int lo = (int)(v & 0xFFFFFFFFll), hi = (int)(v >> 32);
-  lo = __builtin_amdgcn_readlane(lo, src_lane);
-  hi = __builtin_amdgcn_readlane(hi, src_lane);
-  return ((i64)hi << 32) | (unsigned)lo;
-}
-
-// e = q d + r for a SMALL quotient (q < 1024, e < 2^23): an integer division by a run-time divisor costs ~40
-// instructions on gfx950, and these index splits sit in the inner loops of issue-bound kernels.  rd = 1.0f / d.
-__device__ __forceinline__ void divmod_small(int e, int d, float rd, int& q, int& r) {
-  q = (int)(((float)e + 0.5f) * rd);
-  r = e - q * d;
-}
-
 __device__ __forceinline__ double block_sum(double v) {
   __shared__ double ws[16];
   v = wave_sum(v);
@@ -1556,8 +1537,7 @@ __global__ void __launch_bounds__(256) assemble_h_star_kernel(DevProblem P, DevS
       int q, rem, i, j;
       divmod_small(on ? e : 0, nper, rnper, q, rem);
       divmod_small(rem, dB, rdB, j, i);
-      const int lo = __shfl((int)(r_jac & 0xffffffff), q), hi = __shfl((int)(r_jac >> 32), q);
-      const i64 joff = ((i64)hi << 32) | (unsigned)lo;
+      const i64 joff = shfl_i64(r_jac, q);
       const int dst = __shfl(r_dst, q);
       if (on) panel[dst + i + j * rows] = star_entry(jac + joff, m, m == 2 && (joff & 1) == 0, colB + i, colA + j);
     }
@@ -1612,7 +1592,7 @@ __device__ __forceinline__ void assemble_h_star_bundle_body(const DevProblem& P,
   i64 r_jac = 0;
   int r_dst = 0;
   {
-    const i64 t0s = ((i64)__shfl((int)(s_t0 >> 32), f_slot) << 32) | (unsigned)__shfl((int)(s_t0 & 0xffffffff), f_slot);
+    const i64 t0s = shfl_i64(s_t0, f_slot);
     const int fl = lane - __shfl(s_first, f_slot);
     if (lane < nft) {
       r_jac = S.terms[t0s + 3 * (i64)fl].jac;
@@ -1624,7 +1604,7 @@ __device__ __forceinline__ void assemble_h_star_bundle_body(const DevProblem& P,
   const int m = a0.m, colA = a0.colA, colB = b0.colB, dB = b0.dB, colR = c0t.colB;
   const int nper = dB * d, nown = d * d + d;
   const int f_rows = __shfl(s_rows, f_slot);
-  const i64 f_hoff = ((i64)__shfl((int)(s_hoff >> 32), f_slot) << 32) | (unsigned)__shfl((int)(s_hoff & 0xffffffff), f_slot);
+  const i64 f_hoff = shfl_i64(s_hoff, f_slot);
   // level 3: partner blocks, all entries of all factors flat over the lanes
   const float rnper = 1.0f / (float)nper, rdB = 1.0f / (float)dB;
   const int total = nft * nper;
@@ -1634,10 +1614,10 @@ __device__ __forceinline__ void assemble_h_star_bundle_body(const DevProblem& P,
     int q, rem, i, j;
     divmod_small(on ? e : 0, nper, rnper, q, rem);
     divmod_small(rem, dB, rdB, j, i);
-    const i64 joff = ((i64)__shfl((int)(r_jac >> 32), q) << 32) | (unsigned)__shfl((int)(r_jac & 0xffffffff), q);
+    const i64 joff = shfl_i64(r_jac, q);
     const int dst = __shfl(r_dst, q);
     const int rows = __shfl(f_rows, q);
-    const i64 hoff = ((i64)__shfl((int)(f_hoff >> 32), q) << 32) | (unsigned)__shfl((int)(f_hoff & 0xffffffff), q);
+    const i64 hoff = shfl_i64(f_hoff, q);
     if (on) H[hoff + dst + i + j * rows] = star_entry(jac + joff, m, m == 2 && (joff & 1) == 0, colB + i, colA + j);
   }
   // own block and rhs row: a lane per (variable, entry), over that variable's factors in list order
@@ -1647,7 +1627,7 @@ __device__ __forceinline__ void assemble_h_star_bundle_body(const DevProblem& P,
     const bool on = slot < nv;
     const int sl = on ? slot : 0;
     const int rows = __shfl(s_rows, sl), first = __shfl(s_first, sl), nf = __shfl(s_nf, sl);
-    const i64 hoff = ((i64)__shfl((int)(s_hoff >> 32), sl) << 32) | (unsigned)__shfl((int)(s_hoff & 0xffffffff), sl);
+    const i64 hoff = shfl_i64(s_hoff, sl);
     int ci, cj, odst;
     if (ent < d * d) {
       const int i = ent % d, j = ent / d;
@@ -1662,7 +1642,7 @@ __device__ __forceinline__ void assemble_h_star_bundle_body(const DevProblem& P,
     double own = 0.0;
     for (int it = 0; it < nfmax; ++it) {
       const int q = min(first + it, 63);
-      const i64 joff = ((i64)__shfl((int)(r_jac >> 32), q) << 32) | (unsigned)__shfl((int)(r_jac & 0xffffffff), q);
+      const i64 joff = shfl_i64(r_jac, q);
       if (on && it < nf) star_accum(own, jac + joff, m, m == 2 && (joff & 1) == 0, ci, cj);
     }
     if (on) H[hoff + odst] = own;
@@ -2020,128 +2000,10 @@ static bool lds_fits(const void* kernel, size_t dynamic_bytes, const char* what,
 // in-LDS partial Cholesky (choleskyPartial, gtsam/base/cholesky.cpp:108-159), lower form:
 // columns 0..F-1 become [L11; L21] (incl. the rhs row), the trailing block C -= L21 L21'.
 // All threads of the block take part.  Returns (in every thread) 0 ok / 1 failed.
-// ---------------------------------------------------------------------------------------------
-#ifdef GSX_STAMP
-__device__ unsigned long long g_stamp[8];
-#define STAMP_BEGIN unsigned long long st0__ = __builtin_amdgcn_s_memtime();
-#define STAMP_ADD(slot)                                                      \
-  {                                                                          \
-    unsigned long long t__ = __builtin_amdgcn_s_memtime();                   \
-    if (threadIdx.x == 0 && blockIdx.x == 0) g_stamp[slot] += t__ - st0__;   \
-    st0__ = t__;                                                             \
-  }
-#else
-#define STAMP_BEGIN
-#define STAMP_ADD(slot)
-#endif
-template <int PB>
-__device__ inline int lds_partial_cholesky_t(double* L, int n, int F, bool gap_test) {
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
-  int fail = 0;
-  // Blocked right-looking: panels of PB columns are factored with rank-1 updates confined to the
-  // panel (n x PB entries per pivot instead of n x n), then ONE rank-PB sweep updates the rest of the
-  // matrix — 1/PB of the LDS traffic and of the full-matrix passes of the unblocked form.
-  // Inside a panel thread r keeps ROW r of the panel (PB values) in registers; per pivot the only shared
-  // data is column j restricted to the PB x PB diagonal block, double-buffered in LDS => ONE barrier per
-  // pivot (requires blockDim >= n, which the size classes guarantee).
-  __shared__ double dcol[2][PB];
-  const int row = tid;
-  for (int j0 = 0; j0 < F; j0 += PB) {
-    const int pb = min(PB, F - j0), jend = j0 + pb;
-    STAMP_BEGIN
-    const bool active = row >= j0 && row < n;
-    const int dk = row - j0;  // position inside the diagonal block (valid when 0 <= dk < pb)
-    double a[PB];
-#pragma unroll
-    for (int k = 0; k < PB; ++k) a[k] = (active && k < pb) ? L[row + (j0 + k) * n] : 0.0;
-    if (dk >= 0 && dk < pb) dcol[0][dk] = a[0];
-#pragma unroll
-    for (int jj = 0; jj < PB; ++jj) {
-      if (jj < pb) {
-        __syncthreads();
-        const double* cur = dcol[jj & 1];
-        const double p = cur[jj];
-        if (!(p > 0)) fail = 1;  // Eigen::LLT reports NumericalIssue on a non-positive pivot
-        const double inv = (p > 0) ? rsqrt(p) : 1.0;
-        if (active && dk >= jj) {
-          const double l = (dk == jj) ? p * inv : a[jj] * inv;
-          a[jj] = l;
-#pragma unroll
-          for (int k = jj + 1; k < PB; ++k)
-            if (k < pb && dk >= k) a[k] -= l * (cur[k] * inv);
-          if (jj + 1 < pb && dk > jj && dk < pb) dcol[(jj + 1) & 1][dk] = a[jj + 1 < PB ? jj + 1 : 0];
-        }
-      }
-    }
-    if (active) {
-#pragma unroll
-      for (int k = 0; k < PB; ++k)
-        if (k < pb && dk >= k) L[row + (j0 + k) * n] = a[k];
-    }
-    __syncthreads();
-    STAMP_ADD(0)
-    // rank-pb trailing update C -= P P' on the FP64 matrix cores: one wave per 16x16 tile of the lower
-    // triangle, v_mfma_f64_16x16x4 (A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15],
-    // C/D row = (lane>>4) + 4 reg, col = lane&15), two k-steps for the 8-column panel.  Per lane that is
-    // 4 LDS reads of operands + 8 of the C tile for 32 FMA-equivalents (the VALU form needed 18 reads for
-    // 16 FMAs and was bound by the ~100-cycle LDS round trip).
-    {
-      const int m = n - jend, nt16 = (m + 15) >> 4, ntiles = nt16 * (nt16 + 1) / 2;
-      const int li = lane & 15, lk = lane >> 4;
-      for (int t = wave; t < ntiles; t += nw) {
-        int ti = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
-        while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-        while (ti * (ti + 1) / 2 > t) --ti;
-        const int tj = t - ti * (ti + 1) / 2;
-        const int i0 = jend + ti * 16, c0 = jend + tj * 16;
-        const int col = c0 + li;
-        v4d acc;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int rr = i0 + lk + 4 * q;
-          acc[q] = (rr < n && col < n) ? L[rr + col * n] : 0.0;
-        }
-#pragma unroll
-        for (int kk = 0; kk < PB; kk += 4) {
-          if (kk < pb) {  // wave-uniform
-            const int k = kk + lk;
-            const bool kin = k < pb;
-            const double av = (kin && i0 + li < n) ? -L[(i0 + li) + (j0 + k) * n] : 0.0;
-            const double bv = (kin && c0 + li < n) ? L[(c0 + li) + (j0 + k) * n] : 0.0;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int rr = i0 + lk + 4 * q;
-          if (rr < n && col < n) L[rr + col * n] = acc[q];
-        }
-      }
-    }
-    __syncthreads();
-    STAMP_ADD(1)
-  }
-  // conditioning test on the last two pivots — cholesky.cpp:145-158 (the fronts of a tree are tested per REFERENCE
-  // clique by cond_check_kernel instead: a relaxed front holds several)
-  if (!gap_test) return fail;
-  if (F >= 2) {
-    int e2, e1;
-    (void)frexp(L[(F - 2) + (F - 2) * n], &e2);
-    (void)frexp(L[(F - 1) + (F - 1) * n], &e1);
-    if (!(e2 - e1 < 12)) fail = 1;
-  } else if (F == 1) {
-    int e1;
-    (void)frexp(L[0], &e1);
-    if (!(e1 > -12)) fail = 1;
-  }
-  return fail;
-}
-// ---------------------------------------------------------------------------------------------
-// The same partial Cholesky with the sequential part in REGISTERS (the scheme of bigfront.hip's big_diag): the
-// row-per-thread panel above costs ~1300 cycles a pivot (an LDS write -> barrier -> read round, an rsqrt and a chain of
-// dependent LDS reads), 16 us for the 30 frontal scalars of a typical pose-graph front — most of a front's life.
-// Here, per panel of 16 columns:
+// The sequential part runs in REGISTERS (the scheme of bigfront.hip's big_diag); the row-per-thread panel in LDS that it
+// replaced cost ~1300 cycles a pivot (an LDS write -> barrier -> read round, an rsqrt and a chain of dependent LDS
+// reads), 16 us for the 30 frontal scalars of a typical pose-graph front — most of a front's life (DESIGN.md,
+// experiments that lost).  Per panel of 16 columns:
 //   D. wave 0 holds the diagonal 16 x 16 tile in the matrix-core accumulator layout (lane (li, lk): entries (row li,
 //      column 4 q + lk)) and factors it with no LDS traffic and no barrier: per pivot one v_readlane, an rsqrt, and ONE
 //      rank-1 matrix-core update of the tile; an identity tile carried through the same column operations comes out as
@@ -2151,16 +2013,6 @@ __device__ inline int lds_partial_cholesky_t(double* L, int n, int F, bool gap_t
 //   U. rank-16 update of the trailing matrix from the panel's columns, one wave per 16 x 16 tile.
 // Three workgroup barriers a panel (free for the one-wave fronts).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double tile_rsqrt(double d) {  // 1 / sqrt(d) from the hardware seed + one cubic correction
-  const double y0 = __builtin_amdgcn_rsq(d);
-  const double e = fma(-d * y0, y0, 1.0);
-  return fma(y0 * e, fma(e, 0.375, 0.5), y0);
-}
-__device__ __forceinline__ double tile_readlane(double v, int src_lane) {  // src_lane wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-  return __hiloint2double(hi, lo);
-}
 __device__ inline int lds_partial_cholesky_mfma(double* Lm, int n, int F, bool gap_test, FrontScratch& sc) {
   double* Eb = sc.Eb;
   int& failed = sc.failed;
@@ -2186,8 +2038,8 @@ __device__ inline int lds_partial_cholesky_mfma(double* Lm, int n, int F, bool g
         __builtin_amdgcn_sched_barrier(0);
         int lj = li;
         asm volatile("" : "+v"(lj));
-        const double dj = tile_readlane(pt[q], lkj * 16 + j);
-        const double sj = tile_rsqrt(dj);  // (a non-positive pivot makes L_jj a NaN: caught below)
+        const double dj = readlane_f64(pt[q], lkj * 16 + j);
+        const double sj = rsqrt_refined(dj);  // (a non-positive pivot makes L_jj a NaN: caught below)
         const bool colj = lk == lkj;
         const double xj = pt[q] * sj;
         const double xm = (colj && lj >= j) ? xj : 0.0;
@@ -2276,19 +2128,10 @@ __device__ inline int lds_partial_cholesky_mfma(double* Lm, int n, int F, bool g
   }
   return fail;
 }
-// panel width by frontal size: narrow panels keep the per-pivot register work small for the many cliques
-// with a handful of frontal scalars, wide panels halve the number of trailing sweeps of the larger ones
+// (A call of its own on purpose: with the body under this name the compiler stops inlining it into front_small_kernel
+//  and dense_small_kernel — 7 KB out of line, LDS reached through a table — while front_tree_kernel still inlines it.)
 __device__ inline int lds_partial_cholesky(double* L, int n, int F, bool gap_test, FrontScratch& sc) {
-#ifdef GSX_OLD_LDS_CHOLESKY
-  return (F <= 24) ? lds_partial_cholesky_t<8>(L, n, F, gap_test) : lds_partial_cholesky_t<16>(L, n, F, gap_test);
-#else
   return lds_partial_cholesky_mfma(L, n, F, gap_test, sc);
-#endif
-}
-
-__device__ inline void report_failure(DevStatus* status, int front) {
-  atomicAdd(&status->n_fail, 1);
-  atomicMin(&status->first_front, front);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2501,8 +2344,8 @@ __device__ inline int lds_panel_cholesky_mfma(double* Pm, int n, int F, FrontScr
         __builtin_amdgcn_sched_barrier(0);
         int lj = li;
         asm volatile("" : "+v"(lj));
-        const double dj = tile_readlane(pt[q], lkj * 16 + j);
-        const double sj = tile_rsqrt(dj);
+        const double dj = readlane_f64(pt[q], lkj * 16 + j);
+        const double sj = rsqrt_refined(dj);
         const bool colj = lk == lkj;
         const double xj = pt[q] * sj;
         const double xm = (colj && lj >= j) ? xj : 0.0;
@@ -2940,38 +2783,20 @@ void launch_front_small(const DevProblem& P, const DevSymbolic& S, const int* id
 // matrix in LDS, no zeroing of it, no trailing-update sweeps (the reference allocates and sweeps the full
 // (F+S+1)^2 augmented Hessian per landmark: HessianFactor.cpp:240-253, cholesky.cpp:108-143).
 // ---------------------------------------------------------------------------------------------
-// PACK: four cliques a workgroup, a WAVE each (the launch groups whose cliques run with 64 threads: every BAL landmark) —
-// an experiment (see launch_front_leaf): 78 000 one-wave workgroups in 150 us keep a tenth of the chip's wave slots
-// occupied (SQ counters: 3 600 cycles a wave), but starting fewer, larger workgroups does not change that.  The
-// arithmetic of a clique is the same instruction sequence either way.
-template <bool PACK>
-__device__ __forceinline__ void leaf_sync() {
-  if (PACK) {  // one wave: LDS traffic of its lanes is ordered once the counter has drained
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  } else {
-    __syncthreads();
-  }
-}
-template <bool PACK>
-__global__ void front_leaf_kernel(DevProblem P, DevSymbolic S, const LeafRec* recs, int count, int panel_stride,
-                                  const double* H, const double* damp, const double* scalars, double* arena,
-                                  DevStatus* status) {
-  extern __shared__ double leaf_lds[];  // n x F, column-major, ld = n (PACK: four of them, panel_stride apart)
-  const int sub = PACK ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;   // (wave-uniform: the record stays scalar)
-  const int slot = PACK ? (int)blockIdx.x * 4 + sub : (int)blockIdx.x;
-  if (slot >= count) return;   // (PACK: a whole wave; no workgroup barrier below)
-  double* Pn = leaf_lds + (size_t)sub * panel_stride;
+__global__ void front_leaf_kernel(DevProblem P, DevSymbolic S, const LeafRec* recs, int count, const double* H,
+                                  const double* damp, const double* scalars, double* arena, DevStatus* status) {
+  extern __shared__ double leaf_lds[];  // n x F, column-major, ld = n
+  const int slot = (int)blockIdx.x;
+  if (slot >= count) return;
+  double* Pn = leaf_lds;
   const LeafRec rec = recs[slot];
   const int f = rec.front;
   const int n = rec.n, F = rec.F;
-  const int tid = PACK ? (int)(threadIdx.x & 63) : (int)threadIdx.x, nt = PACK ? 64 : (int)blockDim.x;
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
   const int wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
   const double lambda = scalars[SC_LAMBDA];
   for (int e = tid; e < n * F; e += nt) Pn[e] = 0;
-  leaf_sync<PACK>();
+  __syncthreads();
   for (int k = 0; k < rec.nfv; ++k) {
     // the first frontal variable's panel is described by the record itself; further ones (merged leaf cliques of
     // pose graphs) by their VarRec
@@ -3008,21 +2833,21 @@ __global__ void front_leaf_kernel(DevProblem P, DevSymbolic S, const LeafRec* re
         if (dst[u] >= 0) Pn[dst[u]] = x[u];
     }
   }
-  leaf_sync<PACK>();
+  __syncthreads();
   int fail = 0;
   for (int j = 0; j < F; ++j) {
     const double p = Pn[j + j * n];
     if (!(p > 0)) fail = 1;
     const double s = (p > 0) ? sqrt(p) : 1.0;
     const double inv = 1.0 / s;
-    leaf_sync<PACK>();
+    __syncthreads();
     for (int r = j + tid; r < n; r += nt) Pn[r + j * n] = (r == j) ? s : Pn[r + j * n] * inv;
-    leaf_sync<PACK>();
+    __syncthreads();
     for (int c = j + 1 + wave; c < F; c += nw) {
       const double lc = Pn[c + j * n];
       for (int r = c + lane; r < n; r += 64) Pn[r + c * n] -= Pn[r + j * n] * lc;
     }
-    leaf_sync<PACK>();
+    __syncthreads();
   }
   // (choleskyPartial's conditioning test runs per reference clique after the factorization: cond_check_kernel)
   if (fail && tid == 0) report_failure(status, f);
@@ -3094,17 +2919,8 @@ void launch_front_leaf(const DevProblem& P, const DevSymbolic& S, const LeafRec*
                        const double* H, const double* damp, const double* scalars, double* arena, DevStatus* status,
                        hipStream_t st) {
   if (!count) return;
-  // one-wave cliques four to a workgroup while four panels stay a small share of a CU's LDS
-  // MEASURED AND SWITCHED OFF (GSX_LEAF_PACK=1 with GSX_LEAF_SPLIT=1024 turns it on): on BAL-1723 the main-queue launch
-  // goes 148 -> 138 us, the low-priority one 178 -> 346 us, the LM iteration 1.797 -> 1.793 ms (noise) — the leaf launches
-  // are not bound by how fast workgroups start (a thousand waves in flight either way; tools/r03_leaf.sh)
-  static const bool pack_on = std::getenv("GSX_LEAF_PACK") != nullptr;
-  if (pack_on && threads == 64 && (size_t)max_panel * sizeof(double) * 4 <= 32 * 1024)
-    front_leaf_kernel<true><<<(count + 3) / 4, 256, (size_t)max_panel * sizeof(double) * 4, st>>>(
-        P, S, recs, count, max_panel, H, damp, scalars, arena, status);
-  else
-    front_leaf_kernel<false><<<count, threads, (size_t)max_panel * sizeof(double), st>>>(P, S, recs, count, 0, H, damp,
-                                                                                          scalars, arena, status);
+  front_leaf_kernel<<<count, threads, (size_t)max_panel * sizeof(double), st>>>(P, S, recs, count, H, damp, scalars, arena,
+                                                                                  status);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3123,7 +2939,9 @@ void launch_front_leaf(const DevProblem& P, const DevSymbolic& S, const LeafRec*
 // The first 64 factors' and partner rows' loads are all issued before the first product; with evenly spaced factors
 // (StarLeafRec::jstride) they depend on the record alone.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double readlane_f64(double v, int src_lane) {  // src_lane must be wave-uniform
+// (wave_util.h's readlane_f64 splits the double with __double2loint / __double2hiint; this one goes through the integer
+//  read.  The two are different text to the compiler, so this kernel keeps the one it was measured and bit-checked with.)
+__device__ __forceinline__ double readlane_f64_via_i64(double v, int src_lane) {  // src_lane must be wave-uniform
   return __longlong_as_double(readlane_i64(__double_as_longlong(v), src_lane));
 }
 // Where the two-step path stores a value (H panel, LDS) and loads it back, this kernel keeps it in a register: the
@@ -3195,9 +3013,9 @@ __global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, con
 #pragma unroll
       for (int r = 0; r < D; ++r) {
         if (r >= d) break;
-        G[r] += readlane_f64(pg[r], q);
+        G[r] += readlane_f64_via_i64(pg[r], q);
 #pragma unroll
-        for (int c = 0; c <= r; ++c) O[r][c] += readlane_f64(po[r][c], q);
+        for (int c = 0; c <= r; ++c) O[r][c] += readlane_f64_via_i64(po[r][c], q);
       }
     }
   }
@@ -3511,11 +3329,6 @@ void launch_big_init(const DevProblem& P, const DevSymbolic& S, const BigDesc* d
   big_add_h_kernel<<<dim3(max_nfv, count), 128, 0, st>>>(P, S, descs, H, damp, scalars, arena);
 }
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding GLOBAL access
-// (s_waitcnt vmcnt(0)) — which would put the latency of in-flight prefetches and of
-// just-issued stores on the critical path of the latency-bound kernels below.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // (The blocked fronts' factorization kernels live in bigfront.hip.)
 // gsx_cholesky_partial's large case: move the L panel back under the diagonal tiles of the matrix
 __global__ void big_copy_panel_kernel(const BigDesc* descs, double* arena) {
@@ -3693,7 +3506,7 @@ __device__ __forceinline__ void backsolve_leaf_wave(const DevSymbolic& S, const 
   for (int c = 0; c < FM; ++c) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) yc[c] += __shfl_xor(yc[c], o, 64);
-    yc[c] = tile_readlane(dl, c) - yc[c];
+    yc[c] = readlane_f64(dl, c) - yc[c];
   }
   // L11' x = y, backwards (every lane computes the same values)
   double xv[FM];
@@ -3704,8 +3517,8 @@ __device__ __forceinline__ void backsolve_leaf_wave(const DevSymbolic& S, const 
       double acc = yc[c];
 #pragma unroll
       for (int r = c + 1; r < FM; ++r)
-        if (r < F) acc -= (FM <= 8 ? tile_readlane(tri, r + c * F) : A[r + (i64)c * n]) * xv[r];
-      xv[c] = acc / (FM <= 8 ? tile_readlane(tri, c + c * F) : A[c + (i64)c * n]);
+        if (r < F) acc -= (FM <= 8 ? readlane_f64(tri, r + c * F) : A[r + (i64)c * n]) * xv[r];
+      xv[c] = acc / (FM <= 8 ? readlane_f64(tri, c + c * F) : A[c + (i64)c * n]);
     }
   }
   double mine = 0.0;
@@ -3935,16 +3748,6 @@ void launch_dense_partial(double* a, int n, int nf, DevStatus* status, hipStream
       attr = true;
     }
     dense_small_kernel<<<1, 512, (size_t)n * n * sizeof(double), st>>>(a, n, nf, status);
-#ifdef GSX_STAMP
-    {
-      unsigned long long h[8];
-      hipStreamSynchronize(st);
-      hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamp), sizeof(h));
-      printf("[stamp] n=%d F=%d panel-factor %llu cycles, trailing %llu cycles\n", n, nf, h[0], h[1]);
-      unsigned long long z[8] = {0};
-      hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof(z));
-    }
-#endif
     return;
   }
   // the L panel is produced next to the matrix and copied back under the diagonal tiles at the end

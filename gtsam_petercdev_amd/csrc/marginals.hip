@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "wave_util.h"
 
 namespace gsx {
 
@@ -190,12 +191,6 @@ __global__ void __launch_bounds__(256) marg_emit_kernel(DevSymbolic S, MargArgs 
 // frontal columns): a wave per clique, four to a workgroup.  Sigma_FF = X' (I + L21' Sigma_SS L21) X; the separator is
 // walked in strips of 64 rows (a lane per row), whatever its length.
 constexpr int kLeafF = 16;
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __global__ void __launch_bounds__(256) marg_leaf_kernel(DevSymbolic S, MargArgs M, const int* ids, int count) {
   __shared__ double lds[4][64 * kLeafF + 2 * kLeafF * kLeafF];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -19,6 +19,7 @@
 
 #include "kernels.h"
 #include "smart_math.h"
+#include "wave_util.h"
 
 namespace gsx {
 
@@ -87,12 +88,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) smart_linearize_kernel(De
     if (r - 3 < m) out[r - 3] = ok ? x[r] : 0.0;
 }
 
-__device__ __forceinline__ double wave_total(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) smart_error_kernel(DevProblem P, const int* list, int n, SmartDev S, double* partials) {
   __shared__ double ws[4];
   double acc = 0.0;
@@ -105,7 +100,7 @@ __global__ void __launch_bounds__(256) smart_error_kernel(DevProblem P, const in
     acc += smart::reprojection_error(cams, F.z, F.nk, p, F.inv_sigma, &ok);
   }
   // fixed summation order: lanes by shuffle, then the four waves in order
-  acc = wave_total(acc);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) partials[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
