@@ -16,10 +16,12 @@ import numpy as np
 
 # ---- enums (include/gsx.h) -------------------------------------------------
 GSX_OK, GSX_E_INVALID, GSX_E_NO_DEVICE, GSX_E_BAD_ORDERING, GSX_E_INDETERMINATE, GSX_E_STATE, GSX_E_NOMEM = range(7)
-VAR_VECTOR, VAR_POSE2, VAR_POSE3, VAR_CAMERA = range(4)
+VAR_VECTOR, VAR_POSE2, VAR_POSE3, VAR_CAMERA, VAR_ROT3 = range(5)
 F_LINEAR, F_PRIOR, F_BETWEEN, F_SFM, F_PROJECTION, F_BEARINGRANGE, F_RANGE, F_BEARING, F_STEREO, F_SFM2 = range(10)
 F_SMART_PROJECTION = 10
 F_TRANSLATION, F_BILINEAR_TRANSLATION = 11, 12   # gtsam/sfm/TranslationFactor.h
+# absolute-measurement factors: gtsam/navigation/{GPSFactor,AttitudeFactor,MagFactor,MagPoseFactor}.h, gtsam/slam/Pose*Prior.h
+F_GPS, F_POSE_TRANSLATION_PRIOR, F_POSE_ROTATION_PRIOR, F_ATTITUDE, F_MAG = 13, 14, 15, 16, 17
 MFAS_MAX_NODES = 8192    # GSX_MFAS_MAX_NODES
 SMART_MEAS_HEAD = 11   # doubles of a smart factor's meas before body_P_sensor / the pixels (include/gsx.h)
 NOISE_FORMAT_G2O, NOISE_FORMAT_TORO, NOISE_FORMAT_GRAPH, NOISE_FORMAT_COV, NOISE_FORMAT_AUTO = range(5)
@@ -32,8 +34,8 @@ SOLVER_MULTIFRONTAL, SOLVER_PCG = range(2)
 GATHER_SEGMENT_FIELDS = ("group", "task", "front", "var_row", "var_col", "dB", "dA", "diag", "slot", "src_begin", "src_end")
 GATHER_COMBINE_FIELDS = ("group", "task", "slot0", "nslots")
 
-STATE_DIM = {VAR_POSE2: 3, VAR_POSE3: 12, VAR_CAMERA: 17}
-TANGENT_DIM = {VAR_POSE2: 3, VAR_POSE3: 6, VAR_CAMERA: 9}
+STATE_DIM = {VAR_POSE2: 3, VAR_POSE3: 12, VAR_CAMERA: 17, VAR_ROT3: 9}
+TANGENT_DIM = {VAR_POSE2: 3, VAR_POSE3: 6, VAR_CAMERA: 9, VAR_ROT3: 3}
 
 _STATUS_NAMES = {
     GSX_OK: "GSX_OK", GSX_E_INVALID: "GSX_E_INVALID", GSX_E_NO_DEVICE: "GSX_E_NO_DEVICE",
@@ -245,6 +247,7 @@ class ProblemArrays:
         sd = self.var_dims.copy()
         sd[self.var_types == VAR_POSE3] = 12
         sd[self.var_types == VAR_CAMERA] = 17
+        sd[self.var_types == VAR_ROT3] = 9
         return sd
 
     def state_offsets(self) -> np.ndarray:

@@ -175,6 +175,30 @@ struct Symbolic {
   int64_t max_F = 0, max_rows = 0, n_small = 0, n_big = 0, n_medium = 0;
 };
 
+// The refusal line of a call that has no handle (the writers, the initializers, triangulation): gsx_last_error(NULL)
+// returns the calling thread's last one.
+inline std::string& call_error() {
+  static thread_local std::string e;
+  return e;
+}
+// those calls read states by their own rules and know no Rot3: a description that holds a GSX_VAR_ROT3 variable is refused
+inline gsx_status refuse_rot3(const gsx_problem_desc* d, const char* who) {
+  if (d && d->var_types)
+    for (int v = 0; v < d->n_vars; ++v)
+      if (d->var_types[v] == GSX_VAR_ROT3) {
+        call_error() = std::string(who) + ": variable " + std::to_string(v) + " (key " +
+                       std::to_string(d->var_keys ? (unsigned long long)d->var_keys[v] : 0ull) + ") is a GSX_VAR_ROT3";
+        return GSX_E_INVALID;
+      }
+  return GSX_OK;
+}
+
+// entry of a handle-less call that takes a description: the line of an earlier refusal goes, a Rot3 is refused by name
+inline gsx_status enter_call(const gsx_problem_desc* d, const char* who) {
+  call_error().clear();
+  return refuse_rot3(d, who);
+}
+
 // host algorithms
 gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string& err);
 void compute_ordering(const HostProblem& P, int kind, std::vector<int>& order);

@@ -492,6 +492,10 @@ struct Context {
 // ---- what the files that work on a handle share ------------------------------------------------------------------------
 // upload.hip
 int factor_type_list(const HostProblem& P, int f);
+// the ABS_* sub-kind of a TL_ABSOLUTE factor (kernels.h), 0 for every other factor; and a TL_ABSOLUTE list put in the order
+// its kernels want: by sub-kind, graph order inside a kind
+int factor_absolute_kind(const HostProblem& P, int f);
+void sort_absolute_list(const HostProblem& P, std::vector<int>& list);
 void whiten_linear_factor(const HostProblem& P, int f, const double* src, double* J);
 gsx_status upload_problem(gsx_context* c);
 gsx_status upload_symbolic(gsx_context* c);

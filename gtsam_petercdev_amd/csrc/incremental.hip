@@ -93,6 +93,7 @@ gsx_status partial_linearize(gsx_handle h, std::vector<int>& dfac) {
       const int k = factor_type_list(P, f);
       if (k >= 0) lists[k].push_back(f);
     }
+    sort_absolute_list(P, lists[TL_ABSOLUTE]);
     const int* lp[kNumTypeLists];
     int cnt[kNumTypeLists];
     for (int k = 0; k < kNumTypeLists; ++k) {

@@ -101,6 +101,7 @@ inline int64_t desc_state_size(const gsx_problem_desc* d, std::vector<int>* stat
       case GSX_VAR_POSE2: n += 3; break;
       case GSX_VAR_POSE3: n += 12; break;
       case GSX_VAR_CAMERA: n += 17; break;
+      case GSX_VAR_ROT3: n += 9; break;
       default: n += d->var_dims[v];
     }
   }

@@ -273,6 +273,7 @@ void gsx_init_pose3_params_default(gsx_init_pose3_params* p) {
 
 gsx_status gsx_pose3_init_structure(const gsx_problem_desc* desc, int32_t* n_edges, int32_t* edge_from, int32_t* edge_to,
                                     int32_t* adj_ptr, int32_t* adj, int64_t adj_cap) {
+  if (gsx::enter_call(desc, "gsx_pose3_init_structure") != GSX_OK) return GSX_E_INVALID;
   gsx::PoseGraph G;
   std::string err;
   gsx_status st = gsx::build_pose_graph(desc, G, err);

@@ -400,6 +400,7 @@ gsx_status gsx_closest_rotations(const double* m, int64_t n, int32_t device, dou
 }
 
 gsx_status gsx_pose3_orientations_chordal(const gsx_problem_desc* desc, int32_t device, double* rot_out, int64_t n_out) {
+  if (gsx::enter_call(desc, "gsx_pose3_orientations_chordal") != GSX_OK) return GSX_E_INVALID;
   PoseGraph G;
   std::string err;
   gsx_status st = build_pose_graph(desc, G, err);
@@ -422,6 +423,7 @@ gsx_status gsx_pose3_orientations_chordal(const gsx_problem_desc* desc, int32_t 
 gsx_status gsx_pose3_orientations_gradient(const gsx_problem_desc* desc, const double* given, int64_t n_given,
                                            int32_t max_iter, int32_t set_ref_frame, int32_t device, double* rot_out,
                                            int64_t n_out, int32_t* iterations) {
+  if (gsx::enter_call(desc, "gsx_pose3_orientations_gradient") != GSX_OK) return GSX_E_INVALID;
   PoseGraph G;
   std::string err;
   gsx_status st = build_pose_graph(desc, G, err);
@@ -445,6 +447,7 @@ gsx_status gsx_pose3_orientations_gradient(const gsx_problem_desc* desc, const d
 
 gsx_status gsx_pose3_compute_poses(const gsx_problem_desc* desc, const double* rot, int64_t n_rot, int32_t single_iter,
                                    int32_t device, double* values_out, int64_t n_out) {
+  if (gsx::enter_call(desc, "gsx_pose3_compute_poses") != GSX_OK) return GSX_E_INVALID;
   PoseGraph G;
   std::string err;
   gsx_status st = build_pose_graph(desc, G, err);
@@ -464,6 +467,7 @@ gsx_status gsx_pose3_compute_poses(const gsx_problem_desc* desc, const double* r
 gsx_status gsx_initialize_pose3(const gsx_problem_desc* desc, const double* given, int64_t n_given,
                                 const gsx_init_pose3_params* p, int32_t device, double* values_out, int64_t n_out,
                                 int32_t* gradient_iterations) {
+  if (gsx::enter_call(desc, "gsx_initialize_pose3") != GSX_OK) return GSX_E_INVALID;
   gsx_init_pose3_params prm;
   gsx_init_pose3_params_default(&prm);
   if (p) prm = *p;

@@ -827,14 +827,17 @@ gsx_status gsx_read_bal(const char* path, int32_t add_priors, gsx_dataset** out)
 }
 
 gsx_status gsx_save2d(const gsx_problem_desc* d, const double* values, int64_t n_values, const double* model_sigmas, const char* path) {
+  if (gsx::enter_call(d, "gsx_save2d") != GSX_OK) return GSX_E_INVALID;
   GSX_NO_THROW(save2d_impl(d, values, n_values, model_sigmas, path))
 }
 
 gsx_status gsx_write_bal(const gsx_problem_desc* d, const double* values, int64_t n_values, const char* path) {
+  if (gsx::enter_call(d, "gsx_write_bal") != GSX_OK) return GSX_E_INVALID;
   GSX_NO_THROW(write_bal_impl(d, values, n_values, path))
 }
 
 gsx_status gsx_write_g2o(const gsx_problem_desc* d, const double* values, int64_t n_values, const char* path) {
+  if (gsx::enter_call(d, "gsx_write_g2o") != GSX_OK) return GSX_E_INVALID;
   GSX_NO_THROW(write_g2o_impl(d, values, n_values, path))
 }
 

@@ -17,7 +17,8 @@ struct FactorRec {
   i64 jac_off;
   int s0, s1;                 // state offsets of the first two variables (-1: none)
   int meas_off, noise_off;    // doubles into meas / noise
-  int type_kind;              // f_type | noise kind (with the robust bits) << 8 | type of the first variable << 24
+  int type_kind;              // f_type | noise kind (with the robust bits) << 8 | ABS_* sub-kind of a TL_ABSOLUTE factor
+                              // << 16 (0 elsewhere) | type of the first variable << 24
   int rows_dim;               // rows | dimension of the first variable (<= 255) << 8 | columns of [A b] << 16
 };
 // Immutable problem tables on the device (graph order).
@@ -181,7 +182,26 @@ enum { TL_SFM = 0, TL_BETWEEN_POSE2 = 1, TL_BETWEEN_POSE3 = 2, TL_GENERIC = 3, T
        // SmartProjectionPoseFactor<Cal3_S2>: kernels of its own (smart.hip), and state the handle keeps (SmartDev)
        TL_SMART = 19,
        // TranslationFactor and BilinearAngleTranslationFactor (gtsam/sfm/TranslationFactor.h)
-       TL_TRANSLATION = 20, TL_BATA = 21, kNumTypeLists = 22 };
+       TL_TRANSLATION = 20, TL_BATA = 21,
+       // the absolute-measurement factors: every single-key form of GSX_F_GPS, GSX_F_POSE_TRANSLATION_PRIOR,
+       // GSX_F_POSE_ROTATION_PRIOR, GSX_F_ATTITUDE and GSX_F_MAG in one list (sorted by ABS_* sub-kind), and the two
+       // two-key forms that came with them: BetweenFactor<Rot3> and GPSFactorArmCalib
+       TL_ABSOLUTE = 22, TL_BETWEEN_ROT3 = 23, TL_GPS_CALIB = 24, kNumTypeLists = 25 };
+// sub-kind of a TL_ABSOLUTE factor, in bits 16..23 of FactorRec::type_kind (its noise kind keeps bits 8..15)
+enum { ABS_GPS = 0, ABS_GPS_ARM = 1, ABS_TRANS_POSE2 = 2, ABS_TRANS_POSE3 = 3, ABS_ROT_POSE2 = 4, ABS_ROT_POSE3 = 5,
+       ABS_ATT_ROT3 = 6, ABS_ATT_POSE3 = 7, ABS_MAG_ROT3 = 8, ABS_MAG_POSE3 = 9, ABS_MAG_POSE2 = 10 };
+// of a factor of type `t` on a first variable of type vt0 with nmeas doubles in the handle's measurement table (read only
+// for GSX_F_GPS, whose entry is the caller's: upload.hip, factor_type_list); -1: not in that list
+inline int absolute_kind_of(int t, int vt0, int vt1, long long nmeas) {
+  switch (t) {
+    case GSX_F_GPS: return vt1 >= 0 ? -1 : (nmeas > 3 ? ABS_GPS_ARM : ABS_GPS);
+    case GSX_F_POSE_TRANSLATION_PRIOR: return vt0 == GSX_VAR_POSE2 ? ABS_TRANS_POSE2 : ABS_TRANS_POSE3;
+    case GSX_F_POSE_ROTATION_PRIOR: return vt0 == GSX_VAR_POSE2 ? ABS_ROT_POSE2 : ABS_ROT_POSE3;
+    case GSX_F_ATTITUDE: return vt0 == GSX_VAR_ROT3 ? ABS_ATT_ROT3 : ABS_ATT_POSE3;
+    case GSX_F_MAG: return vt0 == GSX_VAR_ROT3 ? ABS_MAG_ROT3 : (vt0 == GSX_VAR_POSE3 ? ABS_MAG_POSE3 : ABS_MAG_POSE2);
+  }
+  return -1;
+}
 constexpr int kSensorListShift = TL_RANGE_POSE2_POINT_SENSOR - TL_RANGE_POSE2_POINT;  // range list -> its sensor form
 // list of a factor of type `t` whose first two variables have types vt0, vt1 and whose measurement has nmeas doubles
 // (the sensor forms are told by their length); -1: GSX_F_LINEAR, no list
@@ -192,7 +212,9 @@ inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
     case GSX_F_SFM2: return TL_SFM2;
     case GSX_F_PROJECTION: return nmeas > 7 ? TL_PROJECTION_SENSOR : TL_PROJECTION;
     case GSX_F_BEARINGRANGE: return TL_BEARINGRANGE;
-    case GSX_F_BETWEEN: return vt0 == GSX_VAR_POSE2 ? TL_BETWEEN_POSE2 : (vt0 == GSX_VAR_POSE3 ? TL_BETWEEN_POSE3 : TL_GENERIC);
+    case GSX_F_BETWEEN:
+      return vt0 == GSX_VAR_POSE2 ? TL_BETWEEN_POSE2
+                                  : (vt0 == GSX_VAR_POSE3 ? TL_BETWEEN_POSE3 : (vt0 == GSX_VAR_ROT3 ? TL_BETWEEN_ROT3 : TL_GENERIC));
     case GSX_F_RANGE:
       return (vt0 == GSX_VAR_POSE2 ? (vt1 == GSX_VAR_POSE2 ? TL_RANGE_POSE2_POSE : TL_RANGE_POSE2_POINT)
                                    : (vt1 == GSX_VAR_POSE3 ? TL_RANGE_POSE3_POSE : TL_RANGE_POSE3_POINT)) +
@@ -202,6 +224,11 @@ inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
     case GSX_F_SMART_PROJECTION: return TL_SMART;
     case GSX_F_TRANSLATION: return TL_TRANSLATION;
     case GSX_F_BILINEAR_TRANSLATION: return TL_BATA;
+    case GSX_F_GPS: return vt1 >= 0 ? TL_GPS_CALIB : TL_ABSOLUTE;
+    case GSX_F_POSE_TRANSLATION_PRIOR:
+    case GSX_F_POSE_ROTATION_PRIOR:
+    case GSX_F_ATTITUDE:
+    case GSX_F_MAG: return TL_ABSOLUTE;
   }
   return TL_GENERIC;
 }

@@ -191,6 +191,14 @@ __device__ inline void local_coords(int type, int dim, const double* x, const do
   } else if (type == GSX_VAR_POSE2) {
     const P2 h = compose(inverse(load_pose2(x)), load_pose2(y));
     out[0] = h.x; out[1] = h.y; out[2] = theta(h);
+  } else if (type == GSX_VAR_ROT3) {  // Rot3 with the Expmap chart: Logmap(x' y)
+    M3 X, Y;
+    for (int i = 0; i < 9; ++i) {
+      X.a[i] = x[i];
+      Y.a[i] = y[i];
+    }
+    const V3 w = so3_logmap(mul(transpose(X), Y));
+    out[0] = w.x; out[1] = w.y; out[2] = w.z;
   } else {
     pose3_logmap(between(load_pose3(x), load_pose3(y)), out);
     if (type == GSX_VAR_CAMERA) {
@@ -628,6 +636,240 @@ __global__ void __launch_bounds__(256) linearize_bata_kernel(DevProblem P, const
   whiten_store<3, 8>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
 }
 
+// ---------------------------------------------------------------------------------------------
+// absolute-measurement factors (TL_ABSOLUTE): every single-key form of GSX_F_GPS, GSX_F_POSE_TRANSLATION_PRIOR,
+// GSX_F_POSE_ROTATION_PRIOR, GSX_F_ATTITUDE and GSX_F_MAG in ONE list, sorted by sub-kind on the host (kernels.h: ABS_*, in
+// bits 16..23 of the record's type_kind), so that a wave diverges only where two kinds meet.  The bodies are a rotation
+// times a vector; e and H (row-major M x D, D the tangent dimension of the key) stay in registers.
+// ---------------------------------------------------------------------------------------------
+// G = -R [b]x (Rot3::rotate's derivative; GPSFactor.cpp:91, Rot3.cpp:115), row-major
+__device__ __forceinline__ void neg_R_skew(const double* R, const double* b, double (&G)[9]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    G[3 * i] = -(R[3 * i + 1] * b[2] - R[3 * i + 2] * b[1]);
+    G[3 * i + 1] = -(R[3 * i + 2] * b[0] - R[3 * i] * b[2]);
+    G[3 * i + 2] = -(R[3 * i] * b[1] - R[3 * i + 1] * b[0]);
+  }
+}
+// e (M) and, when WITH_H, H (M x D row-major) of the sub-kind K at the state x with the measurement z
+template <int K, bool WITH_H, int M, int D>
+__device__ __forceinline__ void absolute_eval(const double* x, const double* z, double (&e)[M], double (&H)[M * D]) {
+  if constexpr (WITH_H) {
+#pragma unroll
+    for (int i = 0; i < M * D; ++i) H[i] = 0.0;
+  }
+  if constexpr (K == ABS_GPS || K == ABS_TRANS_POSE3) {
+    // GPSFactor.cpp:40-43 / PoseTranslationPrior.h:65-77: e = t - z, H = [0 R]
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      e[r] = x[9 + r] - z[r];
+      if constexpr (WITH_H) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) H[r * 6 + 3 + c] = x[3 * r + c];
+      }
+    }
+  } else if constexpr (K == ABS_GPS_ARM) {
+    // GPSFactorArm (GPSFactor.cpp:85-96): e = t + R bL - nT, H = [-R [bL]x, R]; bL follows nT
+    const double b[3] = {z[3], z[4], z[5]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) e[r] = x[9 + r] + (x[3 * r] * b[0] + x[3 * r + 1] * b[1] + x[3 * r + 2] * b[2]) - z[r];
+    if constexpr (WITH_H) {
+      double G[9];
+      neg_R_skew(x, b, G);
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          H[r * 6 + c] = G[3 * r + c];
+          H[r * 6 + 3 + c] = x[3 * r + c];
+        }
+    }
+  } else if constexpr (K == ABS_TRANS_POSE2) {
+    // PoseTranslationPrior<Pose2>: e = (x, y) - z, H = [R 0]
+    e[0] = x[0] - z[0];
+    e[1] = x[1] - z[1];
+    if constexpr (WITH_H) {
+      const double c = cos(x[2]), s = sin(x[2]);
+      H[0] = c; H[1] = -s;
+      H[3] = s; H[4] = c;
+    }
+  } else if constexpr (K == ABS_ROT_POSE2) {
+    // PoseRotationPrior<Pose2> (PoseRotationPrior.h:81-90): e = Rot2 local coordinates of (z, R), H = [0 0 1]
+    const double zz[3] = {0.0, 0.0, z[0]}, xx[3] = {0.0, 0.0, x[2]};
+    e[0] = theta(compose(inverse(load_pose2(zz)), load_pose2(xx)));
+    if constexpr (WITH_H) H[2] = 1.0;
+  } else if constexpr (K == ABS_ROT_POSE3) {
+    // PoseRotationPrior<Pose3>: e = Logmap(z' R), H = [I 0] — the identity as written there, not the Logmap derivative
+    M3 Z, R;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      Z.a[i] = z[i];
+      R.a[i] = x[i];
+    }
+    const V3 w = so3_logmap(mul(transpose(Z), R));
+    e[0] = w.x; e[1] = w.y; e[2] = w.z;
+    if constexpr (WITH_H) H[0] = H[7] = H[14] = 1.0;
+  } else if constexpr (K == ABS_ATT_ROT3 || K == ABS_ATT_POSE3) {
+    // AttitudeFactor::attitudeError (AttitudeFactor.cpp:26-40): q = Unit3(R bMeasured) (normalised, Rot3.cpp:113),
+    // e = B' q with B = nRef.basis() (z + 6, 3 x 2 row-major, from the host); H = B' (I - q q') (-R [b]x): the
+    // reference's B' B_q B_q' (-R [b]x), whatever axis B_q was built from
+    const double b[3] = {z[3], z[4], z[5]};
+    double q[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q[r] = x[3 * r] * b[0] + x[3 * r + 1] * b[1] + x[3 * r + 2] * b[2];
+    const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+    q[0] *= inv; q[1] *= inv; q[2] *= inv;
+    e[0] = z[6] * q[0] + z[8] * q[1] + z[10] * q[2];
+    e[1] = z[7] * q[0] + z[9] * q[1] + z[11] * q[2];
+    if constexpr (WITH_H) {
+      double G[9];
+      neg_R_skew(x, b, G);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double qg = q[0] * G[c] + q[1] * G[3 + c] + q[2] * G[6 + c];
+        const double g0 = G[c] - q[0] * qg, g1 = G[3 + c] - q[1] * qg, g2 = G[6 + c] - q[2] * qg;
+        H[c] = z[6] * g0 + z[8] * g1 + z[10] * g2;
+        H[D + c] = z[7] * g0 + z[9] * g1 + z[11] * g2;
+      }
+    }
+  } else if constexpr (K == ABS_MAG_ROT3 || K == ABS_MAG_POSE3) {
+    // MagFactor1 (MagFactor.h:121-125) / MagPoseFactor<Pose3> (MagPoseFactor.h:118-132): e = R' nM + bias - z,
+    // H = [R' nM]x in the rotation columns (Rot3::unrotate, Rot3.cpp:136-147); z, nM, bias in that order
+    double q[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = x[c] * z[3] + x[3 + c] * z[4] + x[6 + c] * z[5];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) e[r] = (q[r] + z[6 + r]) - z[r];
+    if constexpr (WITH_H) {
+      H[1] = -q[2]; H[2] = q[1];
+      H[D] = q[2]; H[D + 2] = -q[0];
+      H[2 * D] = -q[1]; H[2 * D + 1] = q[0];
+    }
+  } else {
+    static_assert(K == ABS_MAG_POSE2, "sub-kind");
+    // MagPoseFactor<Pose2>: Rot2::unrotate (Rot2.cpp:98-105): q = (c x + s y, -s x + c y), dq / dtheta = (q_y, -q_x)
+    const double c = cos(x[2]), s = sin(x[2]);
+    const double q0 = c * z[2] + s * z[3], q1 = -s * z[2] + c * z[3];
+    e[0] = (q0 + z[4]) - z[0];
+    e[1] = (q1 + z[5]) - z[1];
+    if constexpr (WITH_H) {
+      H[2] = q1;
+      H[5] = -q0;
+    }
+  }
+}
+template <int K, int M, int D>
+__device__ __forceinline__ void absolute_linearize(const FactorRec& fr, const DevProblem& P, const double* values, double* jac) {
+  double e[M], H[M * D], J[M * (D + 1)];
+  absolute_eval<K, true, M, D>(values + fr.s0, P.meas + fr.meas_off, e, H);
+#pragma unroll
+  for (int c = 0; c < D; ++c)
+#pragma unroll
+    for (int r = 0; r < M; ++r) J[c * M + r] = H[r * D + c];
+#pragma unroll
+  for (int r = 0; r < M; ++r) J[D * M + r] = -e[r];
+  whiten_store<M, D + 1>(J, (fr.type_kind >> 8) & 0xff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+template <int K, int M, int D>
+__device__ __forceinline__ double absolute_error(const FactorRec& fr, const DevProblem& P, const double* values) {
+  double e[M], H[M * D];
+  absolute_eval<K, false, M, D>(values + fr.s0, P.meas + fr.meas_off, e, H);
+  return whitened_half_sqnorm<M>(e, (fr.type_kind >> 8) & 0xff, P.noise + fr.noise_off);
+}
+// one switch over the sub-kinds for both kernels: F is called with the kind and its shape as compile-time constants
+#define GSX_ABSOLUTE_DISPATCH(kind, CALL)                     \
+  switch (kind) {                                             \
+    case ABS_GPS: CALL(ABS_GPS, 3, 6); break;                 \
+    case ABS_GPS_ARM: CALL(ABS_GPS_ARM, 3, 6); break;         \
+    case ABS_TRANS_POSE2: CALL(ABS_TRANS_POSE2, 2, 3); break; \
+    case ABS_TRANS_POSE3: CALL(ABS_TRANS_POSE3, 3, 6); break; \
+    case ABS_ROT_POSE2: CALL(ABS_ROT_POSE2, 1, 3); break;     \
+    case ABS_ROT_POSE3: CALL(ABS_ROT_POSE3, 3, 6); break;     \
+    case ABS_ATT_ROT3: CALL(ABS_ATT_ROT3, 2, 3); break;       \
+    case ABS_ATT_POSE3: CALL(ABS_ATT_POSE3, 2, 6); break;     \
+    case ABS_MAG_ROT3: CALL(ABS_MAG_ROT3, 3, 3); break;       \
+    case ABS_MAG_POSE3: CALL(ABS_MAG_POSE3, 3, 6); break;     \
+    case ABS_MAG_POSE2: CALL(ABS_MAG_POSE2, 2, 3); break;     \
+    default: break;                                           \
+  }
+__global__ void __launch_bounds__(256) linearize_absolute_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                 double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+#define GSX_ABS_LIN(K, M, D) absolute_linearize<K, M, D>(fr, P, values, jac)
+  GSX_ABSOLUTE_DISPATCH((fr.type_kind >> 16) & 0xff, GSX_ABS_LIN)
+#undef GSX_ABS_LIN
+}
+__global__ void __launch_bounds__(256) error_absolute_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                             double* partials) {
+  double acc = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const FactorRec fr = P.frec[list[i]];
+#define GSX_ABS_ERR(K, M, D) acc += absolute_error<K, M, D>(fr, P, values)
+    GSX_ABSOLUTE_DISPATCH((fr.type_kind >> 16) & 0xff, GSX_ABS_ERR)
+#undef GSX_ABS_ERR
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+#undef GSX_ABSOLUTE_DISPATCH
+
+// GPSFactorArmCalib (GPSFactor.cpp:113-128): keys (POSE3, VECTOR(3)), the lever arm a variable; e = t + R bL - nT,
+// H1 = [-R [bL]x, R], H2 = R
+__global__ void __launch_bounds__(256) linearize_gps_calib_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                  double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+  const double* x = values + fr.s0;
+  const double* z = P.meas + fr.meas_off;
+  const double b[3] = {values[fr.s1], values[fr.s1 + 1], values[fr.s1 + 2]};
+  double R[9], G[9], J[30];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = x[k];
+  neg_R_skew(R, b, G);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      J[3 * c + r] = G[3 * r + c];
+      J[9 + 3 * c + r] = R[3 * r + c];
+      J[18 + 3 * c + r] = R[3 * r + c];
+    }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) J[27 + r] = -((x[9 + r] + (R[3 * r] * b[0] + R[3 * r + 1] * b[1] + R[3 * r + 2] * b[2])) - z[r]);
+  whiten_store<3, 10>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+
+// BetweenFactor<Rot3> (BetweenFactor.h:111-124) with the identity for the Local derivative, as the Pose3 kernel has it:
+// h = R1' R2, e = Logmap(z' h), A1 = -h' = -R2' R1, A2 = I
+__global__ void __launch_bounds__(256) linearize_between_rot3_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                     double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+  M3 R1, R2, Z;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    R1.a[k] = values[fr.s0 + k];
+    R2.a[k] = values[fr.s1 + k];
+    Z.a[k] = P.meas[fr.meas_off + k];
+  }
+  const M3 h = mul(transpose(R1), R2);
+  const V3 w = so3_logmap(mul(transpose(Z), h));
+  double J[21];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      J[3 * c + r] = -h.a[3 * c + r];  // (-h')(r, c)
+      J[9 + 3 * c + r] = (r == c) ? 1.0 : 0.0;
+    }
+  J[18] = -w.x; J[19] = -w.y; J[20] = -w.z;
+  whiten_store<3, 7>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+
 void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
                       const double* values, double* jac, DevStatus* status, hipStream_t st, const SmartDev* smart) {
   auto grid = [](int n) { return dim3((n + 255) / 256); };
@@ -680,6 +922,9 @@ void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeL
   run_s(linearize_sfm2_kernel, TL_SFM2);
   run(linearize_translation_kernel, TL_TRANSLATION);
   run(linearize_bata_kernel, TL_BATA);
+  run(linearize_absolute_kernel, TL_ABSOLUTE);
+  run(linearize_between_rot3_kernel, TL_BETWEEN_ROT3);
+  run(linearize_gps_calib_kernel, TL_GPS_CALIB);
   if (type_counts[TL_SMART] && smart) {   // triangulate (cache consulted and updated), then marginalize the landmark
     launch_smart_triangulate(P, type_lists[TL_SMART], type_counts[TL_SMART], values, *smart, st);
     launch_smart_linearize(P, type_lists[TL_SMART], type_counts[TL_SMART], *smart, jac, st);
@@ -813,6 +1058,26 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
     double e[3] = {(tb[0] - ta[0]) * a - z[0], (tb[1] - ta[1]) * a - z[1], (tb[2] - ta[2]) * a - z[2]};
     return whitened_half_sqnorm<3>(e, kind, np);
   }
+  if constexpr (FT == GSX_F_GPS) {  // GPSFactorArmCalib: t + R bL - nT, the lever arm the second key
+    const double* x = values + fr.s0;
+    const double* b = values + fr.s1;
+    double e[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) e[r] = (x[9 + r] + (x[3 * r] * b[0] + x[3 * r + 1] * b[1] + x[3 * r + 2] * b[2])) - z[r];
+    return whitened_half_sqnorm<3>(e, kind, np);
+  }
+  if constexpr (FT == GSX_F_BETWEEN && FV == GSX_VAR_ROT3) {  // Logmap(z' R1' R2)
+    M3 R1, R2, Z;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      R1.a[k] = values[fr.s0 + k];
+      R2.a[k] = values[fr.s1 + k];
+      Z.a[k] = z[k];
+    }
+    const V3 w = so3_logmap(mul(transpose(Z), mul(transpose(R1), R2)));
+    double e[3] = {w.x, w.y, w.z};
+    return whitened_half_sqnorm<3>(e, kind, np);
+  }
   const int vt = FV >= 0 ? FV : ((fr.type_kind >> 24) & 0xff);
   if (type == GSX_F_BETWEEN && vt == GSX_VAR_POSE2) {
     const P2 h = compose(inverse(load_pose2(values + fr.s0)), load_pose2(values + fr.s1));
@@ -894,8 +1159,11 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
   for (int k = TL_PROJECTION_SENSOR; k < TL_SMART; ++k) new_lists = new_lists || type_counts[k] > 0;
   // (likewise a graph without smart factors keeps the shares it had before TL_SMART came, and one without the translation
   // factors those it had before TL_TRANSLATION and TL_BATA came)
-  const int held = type_counts[TL_TRANSLATION] + type_counts[TL_BATA] > 0
+  // (and one without the absolute-measurement lists those it had before they came)
+  const int held = type_counts[TL_ABSOLUTE] + type_counts[TL_BETWEEN_ROT3] + type_counts[TL_GPS_CALIB] > 0
                        ? kNumTypeLists
+                   : type_counts[TL_TRANSLATION] + type_counts[TL_BATA] > 0
+                       ? TL_ABSOLUTE
                        : (type_counts[TL_SMART] > 0 ? TL_TRANSLATION : (new_lists ? TL_SMART : TL_PROJECTION_SENSOR));
   int off = 0;
   for (int k = 0; k < kNumTypeLists; ++k) {
@@ -926,6 +1194,9 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
       case TL_SFM2: error_list_kernel<GSX_F_SFM2, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_TRANSLATION: error_list_kernel<GSX_F_TRANSLATION, GSX_VAR_VECTOR><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_BATA: error_list_kernel<GSX_F_BILINEAR_TRANSLATION, GSX_VAR_VECTOR><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_ABSOLUTE: error_absolute_kernel<<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_BETWEEN_ROT3: error_list_kernel<GSX_F_BETWEEN, GSX_VAR_ROT3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_GPS_CALIB: error_list_kernel<GSX_F_GPS, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_SMART:   // triangulate at `values` (cache consulted and updated), then the reprojection errors
         launch_smart_triangulate(P, type_lists[k], n, values, *smart, st);
         launch_smart_error(P, type_lists[k], n, *smart, out, nb, st);
@@ -1153,6 +1424,14 @@ __global__ void __launch_bounds__(256) retract_kernel(DevProblem P, const double
   } else if (type == GSX_VAR_POSE2) {
     const P2 r = compose(load_pose2(x), load_pose2(d));
     y[0] = r.x; y[1] = r.y; y[2] = theta(r);
+  } else if (type == GSX_VAR_ROT3) {  // R Expmap(omega): the rotation part of Pose3::Expmap (SO3.cpp:61-112)
+    const double xi[6] = {d[0], d[1], d[2], 0.0, 0.0, 0.0};
+    M3 X;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) X.a[i] = x[i];
+    const M3 Y = mul(X, pose3_expmap(xi).R);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) y[i] = Y.a[i];
   } else {
     double xi[6];
 #pragma unroll
@@ -1928,7 +2207,7 @@ void launch_mask_copy(const double* in, const unsigned char* mask, int64_t n, do
 }
 
 __device__ inline int state_len(int type, int dim) {
-  return type == GSX_VAR_POSE2 ? 3 : (type == GSX_VAR_POSE3 ? 12 : (type == GSX_VAR_CAMERA ? 17 : dim));
+  return type == GSX_VAR_POSE2 ? 3 : (type == GSX_VAR_POSE3 ? 12 : (type == GSX_VAR_CAMERA ? 17 : (type == GSX_VAR_ROT3 ? 9 : dim)));
 }
 __global__ void scatter_states_kernel(DevProblem P, const int* vars, const int* src_off, int n, const double* src,
                                       double* values) {

@@ -361,16 +361,19 @@ extern "C" {
 
 gsx_status gsx_lago_initialize(const gsx_problem_desc* desc, int32_t use_odometric_path, const double* given,
                                int64_t n_given, int32_t device, double* values_out, int64_t n_out) {
+  if (gsx::enter_call(desc, "gsx_lago_initialize") != GSX_OK) return GSX_E_INVALID;
   return initialize_common(desc, use_odometric_path != 0, false, given, n_given, device, values_out, n_out);
 }
 
 gsx_status gsx_lago_initialize_with_guess(const gsx_problem_desc* desc, const double* given, int64_t n_given, int32_t device,
                                           double* values_out, int64_t n_out) {
+  if (gsx::enter_call(desc, "gsx_lago_initialize_with_guess") != GSX_OK) return GSX_E_INVALID;
   return initialize_common(desc, true, true, given, n_given, device, values_out, n_out);
 }
 
 gsx_status gsx_lago_initialize_orientations(const gsx_problem_desc* desc, int32_t use_odometric_path, int32_t device,
                                             double* theta_out, int64_t n_out) {
+  if (gsx::enter_call(desc, "gsx_lago_initialize_orientations") != GSX_OK) return GSX_E_INVALID;
   LagoGraph G;
   gsx_status st = host_stage(desc, use_odometric_path != 0, G);
   if (st != GSX_OK) return st;
@@ -416,6 +419,7 @@ gsx_status gsx_lago_thetas_to_root(const int32_t* parent, const double* delta, i
 
 gsx_status gsx_lago_regularized_measurements(const gsx_problem_desc* desc, int32_t use_odometric_path, int32_t device,
                                              double* out, int64_t n_out) {
+  if (gsx::enter_call(desc, "gsx_lago_regularized_measurements") != GSX_OK) return GSX_E_INVALID;
   LagoGraph G;
   gsx_status st = host_stage(desc, use_odometric_path != 0, G);
   if (st != GSX_OK) return st;

@@ -383,6 +383,7 @@ extern "C" {
 gsx_status gsx_lago_structure(const gsx_problem_desc* desc, int32_t use_odometric_path, int32_t* n_edges, int32_t* edge_from,
                               int32_t* edge_to, int32_t* parent, double* delta, int32_t* n_tree, int32_t* tree_ids,
                               int32_t* chord_ids, int32_t* max_depth) {
+  if (gsx::enter_call(desc, "gsx_lago_structure") != GSX_OK) return GSX_E_INVALID;
   gsx::LagoGraph G;
   std::string err;
   gsx_status st = gsx::build_lago_graph(desc, G, err);

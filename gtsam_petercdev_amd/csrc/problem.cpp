@@ -12,8 +12,27 @@ static int state_dim(int type, int dim) {
     case GSX_VAR_POSE2: return 3;
     case GSX_VAR_POSE3: return 12;
     case GSX_VAR_CAMERA: return 17;
+    case GSX_VAR_ROT3: return 9;
   }
   return -1;
+}
+
+// Unit3::basis (gtsam/geometry/Unit3.cpp:72-81, 128-138): b1 = normalize(n x axis) with the axis of the smallest |n_i| (ties
+// go to the earlier axis, as the chain of <= there), b2 = n x b1.  B row-major 3 x 2.
+void unit3_basis(const double* n, double* B) {
+  const double mx = std::fabs(n[0]), my = std::fabs(n[1]), mz = std::fabs(n[2]);
+  double a[3] = {0, 0, 0};
+  if (mx <= my && mx <= mz) a[0] = 1;
+  else if (my <= mx && my <= mz) a[1] = 1;
+  else a[2] = 1;
+  double b1[3] = {n[1] * a[2] - n[2] * a[1], n[2] * a[0] - n[0] * a[2], n[0] * a[1] - n[1] * a[0]};
+  const double nrm = std::sqrt(b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2]);
+  for (double& x : b1) x /= nrm;
+  const double b2[3] = {n[1] * b1[2] - n[2] * b1[1], n[2] * b1[0] - n[0] * b1[2], n[0] * b1[1] - n[1] * b1[0]};
+  for (int r = 0; r < 3; ++r) {
+    B[2 * r] = b1[r];
+    B[2 * r + 1] = b2[r];
+  }
 }
 
 gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string& err) {
@@ -38,8 +57,8 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
       return GSX_E_INVALID;
     }
     const int t = P.types[v];
-    const int expect[4] = {P.dims[v], 3, 6, 9};
-    if (t < 0 || t > 3 || P.dims[v] != expect[t] || P.dims[v] <= 0 || (t == GSX_VAR_VECTOR && P.dims[v] > 64)) {
+    const int expect[5] = {P.dims[v], 3, 6, 9, 3};
+    if (t < 0 || t > 4 || P.dims[v] != expect[t] || P.dims[v] <= 0 || (t == GSX_VAR_VECTOR && P.dims[v] > 64)) {
       err = "bad variable type/dim at variable " + std::to_string(v);
       return GSX_E_INVALID;
     }
@@ -63,6 +82,7 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
   P.f_jac_off.resize(nf + 1);
   P.f_cols.resize(nf);
   P.jac_size = 0;
+  bool any_attitude = false;
   for (int f = 0; f < nf; ++f) {
     const int nk = P.f_key_ptr[f + 1] - P.f_key_ptr[f];
     const int m = P.f_rows[f];
@@ -125,7 +145,14 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
         break;
       case GSX_F_SMART_PROJECTION: {  // 2 .. 8 POSE3 keys; 11 doubles, optionally body_P_sensor (12), then 2 nk pixels
         ok = ok && nk >= 2 && nk <= 8 && m == 2 * nk - 3 && (nmeas == 11 + 2 * nk || nmeas == 11 + 12 + 2 * nk);
-        for (int k = 0; ok && k < nk; ++k) ok = tv(k) == GSX_VAR_POSE3;
+        for (int k = 0; ok && k < nk; ++k) {
+          if (tv(k) == GSX_VAR_ROT3) {
+            err = "factor " + std::to_string(f) + ": GSX_F_SMART_PROJECTION on variable " +
+                  std::to_string(P.f_vars[P.f_key_ptr[f] + k]) + ", a GSX_VAR_ROT3 (its keys are POSE3)";
+            return GSX_E_INVALID;
+          }
+          ok = tv(k) == GSX_VAR_POSE3;
+        }
         // SmartFactorBase "needs isotropic"; only ZERO_ON_DEGENERACY (1) of the degeneracy modes
         const int nkind = P.f_noise_kind[f];
         ok = ok && (nkind == GSX_NOISE_UNIT || nkind == GSX_NOISE_ISOTROPIC);
@@ -142,6 +169,32 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
       case GSX_F_BILINEAR_TRANSLATION:
         ok = ok && nk == 3 && tv(0) == GSX_VAR_VECTOR && dv(0) == 3 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 &&
              tv(2) == GSX_VAR_VECTOR && dv(2) == 1 && m == 3 && nmeas == 3;
+        break;
+      case GSX_F_GPS:  // (POSE3): nT, or nT and bL; (POSE3, VECTOR(3)): nT, the lever arm a variable
+        ok = ok && nk >= 1 && m == 3 && tv(0) == GSX_VAR_POSE3 &&
+             ((nk == 1 && (nmeas == 3 || nmeas == 6)) || (nk == 2 && tv(1) == GSX_VAR_VECTOR && dv(1) == 3 && nmeas == 3));
+        break;
+      case GSX_F_POSE_TRANSLATION_PRIOR:
+        ok = ok && nk == 1 && ((tv(0) == GSX_VAR_POSE2 && m == 2) || (tv(0) == GSX_VAR_POSE3 && m == 3)) && nmeas == m;
+        break;
+      case GSX_F_POSE_ROTATION_PRIOR:
+        ok = ok && nk == 1 && ((tv(0) == GSX_VAR_POSE2 && m == 1 && nmeas == 1) || (tv(0) == GSX_VAR_POSE3 && m == 3 && nmeas == 9));
+        break;
+      case GSX_F_ATTITUDE:
+        ok = ok && nk == 1 && (tv(0) == GSX_VAR_ROT3 || tv(0) == GSX_VAR_POSE3) && m == 2 && nmeas == 6;
+        for (int q = 0; ok && q < 2; ++q) {
+          const double* u = P.meas.data() + P.f_meas_ptr[f] + 3 * q;
+          if (!(std::fabs(std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) - 1.0) <= 1e-9)) {
+            err = "factor " + std::to_string(f) + ": " + (q ? "bMeasured" : "nRef") + " of GSX_F_ATTITUDE is not of unit length";
+            return GSX_E_INVALID;
+          }
+        }
+        any_attitude = any_attitude || ok;
+        break;
+      case GSX_F_MAG:
+        ok = ok && nk == 1 &&
+             (((tv(0) == GSX_VAR_ROT3 || tv(0) == GSX_VAR_POSE3) && m == 3) || (tv(0) == GSX_VAR_POSE2 && m == 2)) &&
+             nmeas == 3 * m;
         break;
       default:
         ok = false;
@@ -194,6 +247,23 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
     P.jac_size += (int64_t)m * cols;
   }
   P.f_jac_off[nf] = P.jac_size;
+  // GSX_F_ATTITUDE: B = nRef.basis() (3 x 2 row-major) behind the two directions, computed here once per factor
+  if (any_attitude) {
+    std::vector<double> meas;
+    std::vector<int64_t> ptr(nf + 1, 0);
+    for (int f = 0; f < nf; ++f) {
+      ptr[f] = (int64_t)meas.size();
+      meas.insert(meas.end(), P.meas.begin() + P.f_meas_ptr[f], P.meas.begin() + P.f_meas_ptr[f + 1]);
+      if (P.f_type[f] == GSX_F_ATTITUDE) {
+        double B[6];
+        unit3_basis(P.meas.data() + P.f_meas_ptr[f], B);
+        meas.insert(meas.end(), B, B + 6);
+      }
+    }
+    ptr[nf] = (int64_t)meas.size();
+    P.meas.swap(meas);
+    P.f_meas_ptr.swap(ptr);
+  }
   // Hard-constraint rows on the device: a DIAGONAL model whose constraint rows carry sigma = 1 / sqrt(mu).  Every kernel
   // then treats them as ordinary rows — the graph error gets mu e^2 / 2 for a violated constraint
   // (Constrained::squaredMahalanobisDistance, NoiseModel.cpp:438-444), the linearized error likewise

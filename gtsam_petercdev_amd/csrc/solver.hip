@@ -647,10 +647,12 @@ int32_t gsx_device_count(void) {
 gsx_status gsx_create(const gsx_problem_desc* desc, int32_t device, gsx_handle* out) {
   if (!out) return GSX_E_INVALID;
   *out = nullptr;
+  gsx::call_error().clear();
   gsx_context* c = new gsx_context();
   gsx_status st = lower_problem(desc, c->P, c->err);
   if (st != GSX_OK) {
     std::fprintf(stderr, "gsx_create: %s\n", c->err.c_str());
+    gsx::call_error() = "gsx_create: " + c->err;   // (no handle to ask: gsx_last_error(NULL))
     delete c;
     return st;
   }
@@ -707,7 +709,7 @@ gsx_status gsx_destroy(gsx_handle h) {
   return GSX_OK;
 }
 
-const char* gsx_last_error(gsx_handle h) { return h ? h->err.c_str() : ""; }
+const char* gsx_last_error(gsx_handle h) { return h ? h->err.c_str() : gsx::call_error().c_str(); }
 
 gsx_status gsx_set_ordering(gsx_handle h, const uint64_t* keys, int32_t n) {
   if (!h || (!keys && n > 0)) return GSX_E_INVALID;

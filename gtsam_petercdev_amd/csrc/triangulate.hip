@@ -366,6 +366,7 @@ gsx_status gsx_triangulate(int32_t camera_kind, const double* cameras, int32_t n
 
 gsx_status gsx_triangulation_tracks(const gsx_problem_desc* desc, int32_t* n_landmarks, int64_t* n_observations,
                                     int32_t* landmark_vars, int64_t* track_ptr, int32_t* obs_factor) {
+  if (gsx::enter_call(desc, "gsx_triangulation_tracks") != GSX_OK) return GSX_E_INVALID;
   Grouping G;
   const gsx_status st = group_tracks(desc, G);
   if (st != GSX_OK) return st;
@@ -380,6 +381,7 @@ gsx_status gsx_triangulation_tracks(const gsx_problem_desc* desc, int32_t* n_lan
 gsx_status gsx_triangulate_landmarks(const gsx_problem_desc* desc, const double* values, int64_t n_values,
                                      const gsx_triangulation_params* params, int32_t device, double* values_out,
                                      int32_t* status_out, int32_t* n_landmarks_out) {
+  if (gsx::enter_call(desc, "gsx_triangulate_landmarks") != GSX_OK) return GSX_E_INVALID;
   Grouping G;
   gsx_status st = group_tracks(desc, G);
   if (st != GSX_OK) return st;

@@ -21,12 +21,25 @@ using namespace gsx;
 
 namespace gsx {
 
+// INVARIANT: the length handed to type_list_of / absolute_kind_of is that of the handle's OWN measurement table, which
+// lower_problem lengthens for GSX_F_ATTITUDE (6 doubles from the caller, 12 with B behind them).  Both functions decide by
+// length only for GSX_F_PROJECTION, _STEREO, _RANGE and GSX_F_GPS, whose entries lower_problem leaves as given; a type whose
+// entry it lengthens must not be told apart by length.
 // the list of factor f (kernels.h: type_list_of; the types of its first two variables pick the family's variant, the
 // length of its measurement the form with body_P_sensor)
 int factor_type_list(const HostProblem& P, int f) {
   const int kp = P.f_key_ptr[f], nk = P.f_key_ptr[f + 1] - kp;
   return type_list_of(P.f_type[f], nk > 0 ? P.types[P.f_vars[kp]] : -1, nk > 1 ? P.types[P.f_vars[kp + 1]] : -1,
                       P.f_meas_ptr[f + 1] - P.f_meas_ptr[f]);
+}
+int factor_absolute_kind(const HostProblem& P, int f) {
+  const int kp = P.f_key_ptr[f], nk = P.f_key_ptr[f + 1] - kp;
+  const int k = absolute_kind_of(P.f_type[f], nk > 0 ? P.types[P.f_vars[kp]] : -1, nk > 1 ? P.types[P.f_vars[kp + 1]] : -1,
+                                 P.f_meas_ptr[f + 1] - P.f_meas_ptr[f]);
+  return k < 0 ? 0 : k;
+}
+void sort_absolute_list(const HostProblem& P, std::vector<int>& list) {
+  std::stable_sort(list.begin(), list.end(), [&](int a, int b) { return factor_absolute_kind(P, a) < factor_absolute_kind(P, b); });
 }
 // factor lists of the linearize kernels (one per factor family) and of the error kernels; `owned` (may be null: all)
 // restricts them to the factors this rank evaluates
@@ -40,6 +53,7 @@ gsx_status upload_factor_lists(gsx_context* c, const std::vector<char>* owned) {
     const int k = factor_type_list(P, f);
     if (k >= 0) lists[k].push_back(f);
   }
+  sort_absolute_list(P, lists[TL_ABSOLUTE]);
   for (int k = 0; k < kNumTypeLists; ++k) {
     c->type_count[k] = (int)lists[k].size();
     HIPCHK(c, c->d_type_list[k].upload(lists[k], st));
@@ -208,7 +222,8 @@ gsx_status upload_problem(gsx_context* c) {
       const int v0 = nk > 0 ? P.f_vars[kp] : -1, v1 = nk > 1 ? P.f_vars[kp + 1] : -1;
       fr[f] = FactorRec{(i64)P.f_jac_off[f], v0 >= 0 ? P.state_off[v0] : -1, v1 >= 0 ? P.state_off[v1] : -1,
                         (int)P.f_meas_ptr[f], (int)P.f_noise_ptr[f],
-                        P.f_type[f] | (P.f_noise_kind[f] << 8) | ((v0 >= 0 ? P.types[v0] : 0) << 24),
+                        P.f_type[f] | (P.f_noise_kind[f] << 8) | (factor_absolute_kind(P, f) << 16) |
+                            ((v0 >= 0 ? P.types[v0] : 0) << 24),
                         P.f_rows[f] | (std::min(v0 >= 0 ? P.dims[v0] : 0, 255) << 8) | (P.f_cols[f] << 16)};
     }
     HIPCHK(c, c->d_frec.upload(fr, st));

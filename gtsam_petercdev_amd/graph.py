@@ -89,7 +89,7 @@ def _skew(w):
 
 
 class Rot3:
-    type_code = -1   # (a value InitializePose3 hands out; not a variable type of the backend)
+    type_code = A.VAR_ROT3
     dim = 3
 
     def __init__(self, R=None):
@@ -144,11 +144,32 @@ class Rot3:
     def matrix(self):
         return self.R
 
+    @staticmethod
+    def from_state(s):
+        return Rot3(np.asarray(s[:9]).reshape(3, 3))
+
     def inverse(self):
         return Rot3(self.R.T)
 
     def compose(self, o):
         return Rot3(self.R @ o.R)
+
+    def between(self, o):
+        return Rot3(self.R.T @ o.R)
+
+    def rotate(self, p):
+        return self.R @ _vec3(p)
+
+    def unrotate(self, p):
+        return self.R.T @ _vec3(p)
+
+    def equals(self, o, tol=1e-9):
+        return np.allclose(self.R, o.R, atol=tol)
+
+
+def _vec3(p):
+    """A Point3, or a Unit3's unit vector."""
+    return np.asarray(p.point3() if hasattr(p, "point3") else p, dtype=float).reshape(3)
 
 
 class Pose3:
@@ -255,6 +276,8 @@ def _unwrap(type_code, s):
         return Pose3.from_state(s)
     if type_code == A.VAR_CAMERA:
         return PinholeCameraCal3Bundler.from_state(s)
+    if type_code == A.VAR_ROT3:
+        return Rot3.from_state(s)
     return np.array(s)
 
 
@@ -412,8 +435,8 @@ def BetweenFactor(key1, key2, measured, model=None):
     return f
 
 
-BetweenFactorPose2 = BetweenFactorPose3 = BetweenFactorPoint2 = BetweenFactorPoint3 = BetweenFactor
-PriorFactorPose2 = PriorFactorPose3 = PriorFactorPoint2 = PriorFactorPoint3 = PriorFactor
+BetweenFactorPose2 = BetweenFactorPose3 = BetweenFactorRot3 = BetweenFactorPoint2 = BetweenFactorPoint3 = BetweenFactor
+PriorFactorPose2 = PriorFactorPose3 = PriorFactorRot3 = PriorFactorPoint2 = PriorFactorPoint3 = PriorFactor
 
 
 def GeneralSFMFactor(measured, model, cameraKey, landmarkKey):
@@ -562,6 +585,96 @@ def BilinearAngleTranslationFactor(a, b, scaleKey, w_aZb, model=None):
     return _Factor(A.F_BILINEAR_TRANSLATION, [a, b, scaleKey], 3, _direction(w_aZb), model)
 
 
+# ---- absolute-measurement factors (gtsam/navigation, gtsam/slam/Pose*Prior.h): the reference's argument orders ----------
+def GPSFactor(key, gpsIn, model):
+    """GPSFactor(key, gpsIn, model) — gtsam/navigation/GPSFactor.h: e = translation - gpsIn."""
+    return _Factor(A.F_GPS, [key], 3, _vec3(gpsIn), model)
+
+
+def GPSFactorArm(key, gpsIn, leverArm, model):
+    """GPSFactorArm(key, gpsIn, leverArm, model): e = translation + R leverArm - gpsIn."""
+    return _Factor(A.F_GPS, [key], 3, np.concatenate([_vec3(gpsIn), _vec3(leverArm)]), model)
+
+
+def GPSFactorArmCalib(key1, key2, gpsIn, model):
+    """GPSFactorArmCalib(poseKey, leverArmKey, gpsIn, model): the lever arm is the Point3 variable key2."""
+    return _Factor(A.F_GPS, [key1, key2], 3, _vec3(gpsIn), model)
+
+
+def PoseTranslationPrior2D(key, measured, model):
+    """PoseTranslationPrior<Pose2>(key, translation | pose, model) — gtsam/slam/PoseTranslationPrior.h."""
+    t = np.array([measured.x(), measured.y()]) if isinstance(measured, Pose2) else np.asarray(measured, dtype=float).reshape(2)
+    return _Factor(A.F_POSE_TRANSLATION_PRIOR, [key], 2, t, model)
+
+
+def PoseTranslationPrior3D(key, measured, model):
+    """PoseTranslationPrior<Pose3>(key, translation | pose, model)."""
+    t = measured.translation() if isinstance(measured, Pose3) else _vec3(measured)
+    return _Factor(A.F_POSE_TRANSLATION_PRIOR, [key], 3, t, model)
+
+
+def PoseRotationPrior2D(key, measured, model):
+    """PoseRotationPrior<Pose2>(key, rotation angle | pose, model) — gtsam/slam/PoseRotationPrior.h."""
+    th = measured.theta() if isinstance(measured, Pose2) else float(measured)
+    return _Factor(A.F_POSE_ROTATION_PRIOR, [key], 1, [th], model)
+
+
+def PoseRotationPrior3D(key, measured, model):
+    """PoseRotationPrior<Pose3>(key, Rot3 | pose, model)."""
+    R = measured.rotation() if isinstance(measured, Pose3) else measured
+    return _Factor(A.F_POSE_ROTATION_PRIOR, [key], 3, R.state(), model)
+
+
+def _unit3_vector(u):
+    return (u if isinstance(u, Unit3) else Unit3(u)).point3()
+
+
+def Rot3AttitudeFactor(key, nRef, model, bMeasured=None):
+    """Rot3AttitudeFactor(key, nRef, model, bMeasured = Unit3(0, 0, 1)) — gtsam/navigation/AttitudeFactor.h:96-100."""
+    b = _unit3_vector(bMeasured if bMeasured is not None else Unit3(0.0, 0.0, 1.0))
+    f = _Factor(A.F_ATTITUDE, [key], 2, np.concatenate([_unit3_vector(nRef), b]), model)
+    f.value_type = A.VAR_ROT3
+    return f
+
+
+def Pose3AttitudeFactor(key, nRef, model, bMeasured=None):
+    """Pose3AttitudeFactor(key, nRef, model, bMeasured = Unit3(0, 0, 1)) — AttitudeFactor.h:178-182."""
+    f = Rot3AttitudeFactor(key, nRef, model, bMeasured)
+    f.value_type = A.VAR_POSE3
+    return f
+
+
+def MagFactor1(key, measured, scale, direction, bias, model):
+    """MagFactor1(key, measured, scale, direction, bias, model) — gtsam/navigation/MagFactor.h:105-110: nM = scale * direction
+    (a Unit3)."""
+    return _Factor(A.F_MAG, [key], 3, np.concatenate([_vec3(measured), float(scale) * _unit3_vector(direction), _vec3(bias)]),
+                   model)
+
+
+def _mag_pose(key, measured, scale, direction, bias, model, body_P_sensor, n):
+    # MagPoseFactor's constructor (gtsam/navigation/MagPoseFactor.h:74-85): z and bias rotated into the body frame,
+    # nM = scale * direction.normalized()
+    z, d, b = (np.asarray(v, dtype=float).reshape(n) for v in (measured, direction, bias))
+    if body_P_sensor is not None:
+        if n == 3:
+            R = body_P_sensor.rotation().matrix()
+        else:
+            c, s = math.cos(body_P_sensor.theta()), math.sin(body_P_sensor.theta())
+            R = np.array([[c, -s], [s, c]])
+        z, b = R @ z, R @ b
+    return _Factor(A.F_MAG, [key], n, np.concatenate([z, float(scale) * (d / np.linalg.norm(d)), b]), model)
+
+
+def MagPoseFactorPose2(pose_key, measured, scale, direction, bias, model, body_P_sensor=None):
+    """MagPoseFactor<Pose2>(pose_key, measured, scale, direction, bias, model, body_P_sensor)."""
+    return _mag_pose(pose_key, measured, scale, direction, bias, model, body_P_sensor, 2)
+
+
+def MagPoseFactorPose3(pose_key, measured, scale, direction, bias, model, body_P_sensor=None):
+    """MagPoseFactor<Pose3>(pose_key, measured, scale, direction, bias, model, body_P_sensor)."""
+    return _mag_pose(pose_key, measured, scale, direction, bias, model, body_P_sensor, 3)
+
+
 class Cal3_S2Stereo:
     """gtsam/geometry/Cal3_S2Stereo.h: (fx, fy, s, u0, v0, b)."""
 
@@ -655,7 +768,7 @@ class Values:
         v = self._v[int(key)]
         return v.v.copy() if isinstance(v, _Vector) else v
 
-    atPose2 = atPose3 = atPoint2 = atPoint3 = atVector = at
+    atPose2 = atPose3 = atRot3 = atPoint2 = atPoint3 = atVector = at
 
     def dims(self):
         return {k: self._v[k].dim for k in self.keys()}

@@ -87,8 +87,13 @@ enum {
   GSX_VAR_VECTOR = 0, /* R^d: state d, tangent d (Point2/Point3/generic)       */
   GSX_VAR_POSE2 = 1,  /* state (x,y,theta), tangent (x,y,theta)                */
   GSX_VAR_POSE3 = 2,  /* state R row-major 9 + t 3, tangent (omega3, v3)       */
-  GSX_VAR_CAMERA = 3  /* PinholeCamera<Cal3Bundler>: Pose3 state 12 +          */
+  GSX_VAR_CAMERA = 3, /* PinholeCamera<Cal3Bundler>: Pose3 state 12 +          */
                       /* (f,k1,k2,u0,v0); tangent (pose 6, f, k1, k2)          */
+  GSX_VAR_ROT3 = 4    /* Rot3: state R row-major 9, tangent omega 3; retract R Expmap(omega), local
+                         coordinates Logmap(R1' R2) (gtsam/geometry/Rot3.h:40-47 with GTSAM_ROT3_EXPMAP, the
+                         reference's default).  Taken by GSX_F_PRIOR, GSX_F_BETWEEN, GSX_F_ATTITUDE and GSX_F_MAG;
+                         the g2o / BAL writers, gsx_initialize_pose3, gsx_lago_*, gsx_triangulate_landmarks and
+                         smart factors refuse a problem that holds one (GSX_E_INVALID)                      */
 };
 
 /* ---- factor types -------------------------------------------------------- */
@@ -99,7 +104,9 @@ enum {
                                meas = prior value in the variable's state layout  */
   GSX_F_BETWEEN = 2,        /* BetweenFactor<T> (gtsam/slam/BetweenFactor.h:111-124);
                                meas = measured T in state layout; T in
-                               {VECTOR, POSE2, POSE3}                              */
+                               {VECTOR, POSE2, POSE3, ROT3}.  On ROT3: e =
+                               Logmap(z' R1' R2), A1 = -R2' R1, A2 = I — the identity
+                               for the Local derivative, as on POSE3               */
   GSX_F_SFM = 3,            /* GeneralSFMFactor<PinholeCamera<Cal3Bundler>,Point3>
                                (gtsam/slam/GeneralSFMFactor.h:141-177); keys
                                (camera, point); meas = (u,v)                       */
@@ -194,10 +201,35 @@ enum {
                                Point3.cpp:52-62), H1 = -H2.  Ta == Tb divides by zero exactly as the reference does: no
                                special case — the non-finite block surfaces through the handle's existing non-finite
                                reporting (a failed factorization / GSX_E_INDETERMINATE, a non-finite error)            */
-  GSX_F_BILINEAR_TRANSLATION = 12 /* BilinearAngleTranslationFactor (TranslationFactor.h:104-149), BATA; keys (VECTOR(3),
+  GSX_F_BILINEAR_TRANSLATION = 12, /* BilinearAngleTranslationFactor (TranslationFactor.h:104-149), BATA; keys (VECTOR(3),
                                VECTOR(3), VECTOR(1)) = (Ta, Tb, scale); m = 3; meas = the same 3 doubles.  Error =
                                |s| (Tb - Ta) - z; H1 = -|s| I, H2 = |s| I, H3 = (Tb - Ta) for s >= 0 — s == 0 takes this
                                branch — else (Ta - Tb)                                                                 */
+  /* ---- absolute-measurement factors: one key (GPSFactorArmCalib: two), told apart by key type and length ---- */
+  GSX_F_GPS = 13,           /* GPSFactor (gtsam/navigation/GPSFactor.cpp:40-43): key (POSE3); m = 3; meas = nT (3); e =
+                               t - nT, H = [0 R].  GPSFactorArm (:85-96): meas = nT (3), bL (3) — told by the length; e =
+                               t + R bL - nT, H = [-R [bL]x, R].  GPSFactorArmCalib (:113-128): keys (POSE3, VECTOR(3)),
+                               the lever arm a variable; meas = nT (3); H2 = R                                          */
+  GSX_F_POSE_TRANSLATION_PRIOR = 14, /* PoseTranslationPrior<POSE> (gtsam/slam/PoseTranslationPrior.h:65-77): key (POSE2),
+                               m = 2, meas = (x, y), or (POSE3), m = 3, meas = t (3); e = t - z, H = R in the translation
+                               columns, zero elsewhere                                                                  */
+  GSX_F_POSE_ROTATION_PRIOR = 15, /* PoseRotationPrior<POSE> (gtsam/slam/PoseRotationPrior.h:81-90): key (POSE2), m = 1,
+                               meas = (theta): e = Rot2 local coordinates of (z, R), an angle in (-pi, pi]; or (POSE3),
+                               m = 3, meas = R row-major (9): e = Logmap(z' R).  H is the IDENTITY in the rotation
+                               columns, as written there — not the derivative of Logmap                                */
+  GSX_F_ATTITUDE = 16,      /* Rot3AttitudeFactor / Pose3AttitudeFactor (gtsam/navigation/AttitudeFactor.cpp:26-40,
+                               AttitudeFactor.h:136, 212): key (ROT3) or (POSE3); m = 2; meas = nRef (3), bMeasured (3),
+                               both of unit length to 1e-9 (GSX_E_INVALID otherwise).  e = B' q with q = normalize(R
+                               bMeasured) and B = nRef.basis() (gtsam/geometry/Unit3.cpp:72-141, 199-206), computed by
+                               the library once per factor; H = B' (I - q q') (-R [bMeasured]x) in the rotation columns,
+                               which is the reference's B' B_q B_q' (-R [b]x) for any basis B_q of q; the translation
+                               columns of the POSE3 form are zero                                                       */
+  GSX_F_MAG = 17            /* MagFactor1 (gtsam/navigation/MagFactor.h:121-125): key (ROT3), m = 3; MagPoseFactor<POSE>
+                               (MagPoseFactor.h:74-132): key (POSE3), m = 3, or (POSE2), m = 2.  meas = z, nM, bias, m
+                               doubles each, PREPARED: nM = scale * direction.normalized(), z and bias rotated by
+                               body_P_sensor where there is one (the constructors do that; the Python classes too).
+                               e = R' nM + bias - z; H = [R' nM]x in the rotation columns (Rot3::unrotate), on POSE2
+                               (q_y, -q_x) in the theta column (Rot2::unrotate)                                         */
 };
 
 /* ---- noise model kinds (gtsam/linear/NoiseModel.cpp) --------------------- */
@@ -404,7 +436,15 @@ gsx_status gsx_write_bal(const gsx_problem_desc* desc, const double* values, int
 /* ---- lifecycle ------------------------------------------------------------ */
 gsx_status gsx_create(const gsx_problem_desc* desc, int32_t device, gsx_handle* out);
 gsx_status gsx_destroy(gsx_handle h);
-const char* gsx_last_error(gsx_handle h);          /* human-readable, may be "" */
+const char* gsx_last_error(gsx_handle h);          /* human-readable, may be "".  h == NULL: the line of the
+                                                      calling thread's last call that HAS no handle — a refused
+                                                      gsx_create, and every call that takes a description without
+                                                      one (the g2o / BAL / save2d writers, gsx_pose3_* and
+                                                      gsx_initialize_pose3, gsx_lago_*, gsx_triangulation_tracks,
+                                                      gsx_triangulate_landmarks).  Each of them clears the line on
+                                                      entry, so "" after one that went through or that failed
+                                                      without a line; the pointer is valid until the thread's next
+                                                      such call */
 const char* gsx_version(void);
 int32_t gsx_device_count(void);                    /* 0 when no GPU is visible  */
 

@@ -28,6 +28,10 @@
 #include <gtsam/geometry/Pose2.h>
 #include <gtsam/geometry/Pose3.h>
 #include <gtsam/linear/GaussianFactorGraph.h>
+#include <gtsam/navigation/AttitudeFactor.h>
+#include <gtsam/navigation/GPSFactor.h>
+#include <gtsam/slam/PoseRotationPrior.h>
+#include <gtsam/slam/PoseTranslationPrior.h>
 #include <gtsam/linear/JacobianFactor.h>
 #include <gtsam/linear/NoiseModel.h>
 #include <gtsam/linear/PCGSolver.h>
@@ -93,6 +97,11 @@ inline void pack(const gtsam::Pose3& p, std::vector<double>& out) {
     for (int c = 0; c < 3; ++c) out.push_back(R(r, c));  // row-major
   const gtsam::Point3 t = p.translation();
   out.insert(out.end(), {t.x(), t.y(), t.z()});
+}
+inline void pack(const gtsam::Rot3& r, std::vector<double>& out) {
+  const gtsam::Matrix3 R = r.matrix();
+  for (int i = 0; i < 3; ++i)
+    for (int c = 0; c < 3; ++c) out.push_back(R(i, c));  // row-major
 }
 inline void pack(const gtsam::Vector& v, std::vector<double>& out) { out.insert(out.end(), v.data(), v.data() + v.size()); }
 inline void pack(const gtsam::PinholeCamera<gtsam::Cal3Bundler>& c, std::vector<double>& out) {
@@ -201,7 +210,34 @@ inline bool lower_factor(const gtsam::NonlinearFactor::shared_ptr& f, Lowered& L
     m = {z.uL(), z.uR(), z.v(), K.fx(), K.fy(), K.skew(), K.px(), K.py(), K.baseline()};
     if (sf->body_P_sensor()) pack(*sf->body_P_sensor(), m);  // the 21-double form
     L.add_factor(GSX_F_STEREO, 3, ks, m, kind, np);
+  } else if (auto pr3 = std::dynamic_pointer_cast<PriorFactor<Rot3>>(f)) {
+    pack(pr3->prior(), m), L.add_factor(GSX_F_PRIOR, 3, ks, m, kind, np);
+  } else if (auto br3 = std::dynamic_pointer_cast<BetweenFactor<Rot3>>(f)) {
+    pack(br3->measured(), m), L.add_factor(GSX_F_BETWEEN, 3, ks, m, kind, np);
+  } else if (auto ga = std::dynamic_pointer_cast<GPSFactorArm>(f)) {      // (told from GPSFactor by the 6 doubles)
+    pack(Vector(ga->measurementIn()), m), pack(Vector(ga->leverArm()), m), L.add_factor(GSX_F_GPS, 3, ks, m, kind, np);
+  } else if (auto gc = std::dynamic_pointer_cast<GPSFactorArmCalib>(f)) {  // keys (pose, lever arm)
+    pack(Vector(gc->measurementIn()), m), L.add_factor(GSX_F_GPS, 3, ks, m, kind, np);
+  } else if (auto gp = std::dynamic_pointer_cast<GPSFactor>(f)) {
+    pack(Vector(gp->measurementIn()), m), L.add_factor(GSX_F_GPS, 3, ks, m, kind, np);
+  } else if (auto t2 = std::dynamic_pointer_cast<PoseTranslationPrior<Pose2>>(f)) {
+    pack(Vector(t2->measured()), m), L.add_factor(GSX_F_POSE_TRANSLATION_PRIOR, 2, ks, m, kind, np);
+  } else if (auto t3 = std::dynamic_pointer_cast<PoseTranslationPrior<Pose3>>(f)) {
+    pack(Vector(t3->measured()), m), L.add_factor(GSX_F_POSE_TRANSLATION_PRIOR, 3, ks, m, kind, np);
+  } else if (auto q2 = std::dynamic_pointer_cast<PoseRotationPrior<Pose2>>(f)) {
+    L.add_factor(GSX_F_POSE_ROTATION_PRIOR, 1, ks, {q2->measured().theta()}, kind, np);
+  } else if (auto q3 = std::dynamic_pointer_cast<PoseRotationPrior<Pose3>>(f)) {
+    pack(q3->measured(), m), L.add_factor(GSX_F_POSE_ROTATION_PRIOR, 3, ks, m, kind, np);
+  } else if (auto ar = std::dynamic_pointer_cast<Rot3AttitudeFactor>(f)) {  // nRef, bMeasured: the library computes nRef.basis()
+    pack(Vector(ar->nRef().unitVector()), m), pack(Vector(ar->bMeasured().unitVector()), m);
+    L.add_factor(GSX_F_ATTITUDE, 2, ks, m, kind, np);
+  } else if (auto ap = std::dynamic_pointer_cast<Pose3AttitudeFactor>(f)) {
+    pack(Vector(ap->nRef().unitVector()), m), pack(Vector(ap->bMeasured().unitVector()), m);
+    L.add_factor(GSX_F_ATTITUDE, 2, ks, m, kind, np);
   } else {
+    // MagFactor1 and MagPoseFactor<POSE> have device kernels too (GSX_F_MAG) but keep measured_, nM_ and bias_ private with
+    // no accessors (gtsam/navigation/MagFactor.h:93-96, MagPoseFactor.h:40-48): a caller that knows them lowers the factor by
+    // hand with lower_mag below; found in a graph, it stays a GSX_F_LINEAR slot.
     // RangeFactorWithTransform<A1, A2> has device kernels too (GSX_F_RANGE with 1 + 12 / 1 + 3 measurement doubles) but keeps
     // body_T_sensor_ private with no accessor (gtsam/sam/RangeFactor.h:109): a caller that knows the sensor pose lowers it
     // by hand with lower_range_with_transform below; found in a graph, it stays a GSX_F_LINEAR slot.
@@ -220,6 +256,19 @@ inline bool lower_range_with_transform(const gtsam::NoiseModelFactor& f, double 
   return true;
 }
 
+// MagFactor1 / MagPoseFactor<Pose3> (n = 3) / MagPoseFactor<Pose2> (n = 2) given what their constructors keep: measured and
+// bias already rotated by body_P_sensor where there is one, nM = scale * direction.normalized() (MagPoseFactor.h:74-85)
+inline bool lower_mag(const gtsam::NoiseModelFactor& f, const gtsam::Vector& measured, const gtsam::Vector& nM,
+                      const gtsam::Vector& bias, Lowered& L) {
+  int kind;
+  const int n = (int)measured.size();
+  std::vector<double> np, m;
+  if ((n != 2 && n != 3) || nM.size() != n || bias.size() != n || !lower_noise(f.noiseModel(), n, kind, np)) return false;
+  pack(measured, m), pack(nM, m), pack(bias, m);
+  L.add_factor(GSX_F_MAG, n, std::vector<Key>(f.keys().begin(), f.keys().end()), m, kind, np);
+  return true;
+}
+
 // variable table + packed Values
 inline void lower_values(const gtsam::Values& values, Lowered& L, std::vector<double>& packed) {
   using namespace gtsam;
@@ -229,6 +278,7 @@ inline void lower_values(const gtsam::Values& values, Lowered& L, std::vector<do
     L.keys.push_back(k);
     if (auto p = dynamic_cast<const GenericValue<Pose2>*>(&kv.value)) L.types.push_back(GSX_VAR_POSE2), L.dims.push_back(3), pack(p->value(), packed);
     else if (auto q = dynamic_cast<const GenericValue<Pose3>*>(&kv.value)) L.types.push_back(GSX_VAR_POSE3), L.dims.push_back(6), pack(q->value(), packed);
+    else if (auto r3 = dynamic_cast<const GenericValue<Rot3>*>(&kv.value)) L.types.push_back(GSX_VAR_ROT3), L.dims.push_back(3), pack(r3->value(), packed);
     else if (auto c = dynamic_cast<const GenericValue<PinholeCamera<Cal3Bundler>>*>(&kv.value)) L.types.push_back(GSX_VAR_CAMERA), L.dims.push_back(9), pack(c->value(), packed);
     else if (auto x = dynamic_cast<const GenericValue<Point3>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(3), pack(Vector(x->value()), packed);
     else if (auto y = dynamic_cast<const GenericValue<Point2>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(2), pack(Vector(y->value()), packed);
@@ -247,15 +297,17 @@ inline gtsam::Values unpack_values(const gtsam::Values& like, const std::vector<
   using namespace gtsam;
   Values out;
   size_t o = 0;
-  auto pose3 = [&](size_t at) {
+  auto rot3 = [&](size_t at) {
     Matrix3 R;
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) R(r, c) = packed[at + 3 * r + c];
-    return Pose3(Rot3(R), Point3(packed[at + 9], packed[at + 10], packed[at + 11]));
+    return Rot3(R);
   };
+  auto pose3 = [&](size_t at) { return Pose3(rot3(at), Point3(packed[at + 9], packed[at + 10], packed[at + 11])); };
   for (const auto& kv : like) {
     if (dynamic_cast<const GenericValue<Pose2>*>(&kv.value)) out.insert(kv.key, Pose2(packed[o], packed[o + 1], packed[o + 2])), o += 3;
     else if (dynamic_cast<const GenericValue<Pose3>*>(&kv.value)) out.insert(kv.key, pose3(o)), o += 12;
+    else if (dynamic_cast<const GenericValue<Rot3>*>(&kv.value)) out.insert(kv.key, rot3(o)), o += 9;
     else if (dynamic_cast<const GenericValue<PinholeCamera<Cal3Bundler>>*>(&kv.value)) {
       out.insert(kv.key, PinholeCamera<Cal3Bundler>(pose3(o), Cal3Bundler(packed[o + 12], packed[o + 13], packed[o + 14], packed[o + 15], packed[o + 16])));
       o += 17;
