@@ -33,6 +33,9 @@ SOLVER_MULTIFRONTAL, SOLVER_PCG = range(2)
 # columns of gsx_get_gather_plan's segment and combine records
 GATHER_SEGMENT_FIELDS = ("group", "task", "front", "var_row", "var_col", "dB", "dA", "diag", "slot", "src_begin", "src_end")
 GATHER_COMBINE_FIELDS = ("group", "task", "slot0", "nslots")
+# classes of gsx_get_hessian_groups (-1: a variable of another rank's subtree)
+H_TILE, H_LIGHT, H_HEAVY, H_HUGE, H_STAR, H_DIAG = range(6)
+HESSIAN_CLASS_NAMES = ("tile", "light", "heavy", "huge", "star", "diag")
 
 STATE_DIM = {VAR_POSE2: 3, VAR_POSE3: 12, VAR_CAMERA: 17, VAR_ROT3: 9}
 TANGENT_DIM = {VAR_POSE2: 3, VAR_POSE3: 6, VAR_CAMERA: 9, VAR_ROT3: 3}

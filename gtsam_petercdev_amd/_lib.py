@@ -112,6 +112,34 @@ class ProductBackend(A.Backend):
                 "sources": [(int(c), int(f)) for c, f in src[:nsrc.value]],
                 "combines": [dict(zip(A.GATHER_COMBINE_FIELDS, (int(v) for v in row))) for row in comb[:nm.value]]}
 
+    def hessian_groups(self) -> dict:
+        """gsx_get_hessian_groups: per variable (index as in get_tree) "class" (A.H_TILE ... A.H_DIAG, -1 = another rank's),
+        "group", "position", "bundle", "bundle_size" (star variables; -1 / 0 when unbundled), and "fused_diag_star" for
+        the handle.  Host side: also answers on a host_only handle."""
+        n = max(self.arrays.n_vars, 1)
+        cols = {k: np.full(n, -1, np.int32) for k in ("class", "group", "position", "bundle", "bundle_size")}
+        fused = C.c_int32()
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._fn("get_hessian_groups")(self._h, ip(cols["class"]), ip(cols["group"]), ip(cols["position"]),
+                                                   ip(cols["bundle"]), ip(cols["bundle_size"]), C.byref(fused)),
+                    "get_hessian_groups")
+        out = {k: a[:self.arrays.n_vars] for k, a in cols.items()}
+        out["fused_diag_star"] = bool(fused.value)
+        return out
+
+    def hessian_panel(self, key):
+        """gsx_get_hessian_panel: (panel[rows, dim], row_var[rows], row_scalar[rows]) of variable `key` as assembled on the
+        device; the last row is the right-hand side (row_var -1)."""
+        rows, dim = C.c_int32(), C.c_int32()
+        fn = self._fn("get_hessian_panel")
+        self._check(fn(self._h, C.c_uint64(int(key)), C.byref(rows), C.byref(dim), None, None, None), "get_hessian_panel")
+        out = np.zeros(rows.value * dim.value)
+        rv, rs = np.zeros(rows.value, np.int32), np.zeros(rows.value, np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(fn(self._h, C.c_uint64(int(key)), C.byref(rows), C.byref(dim), out.ctypes.data_as(C.POINTER(C.c_double)),
+                       ip(rv), ip(rs)), "get_hessian_panel")
+        return out.reshape(dim.value, rows.value).T, rv, rs
+
     def shard_probe_buffer(self):
         """(device address, doubles) of a buffer the library hipMalloc'd itself and that holds nothing between calls — what
         distributed.checked_allreduce probes the in-place collective on (gsx_scratch_buffer)."""

@@ -208,6 +208,7 @@ struct Context {
   };
   std::vector<HGroup> hgroups;
   DevBuf<int2> d_star_bundles;   // bundles of the star group (positions relative to the group's variable list)
+  std::vector<int2> h_star_bundles;   // the host's copy (gsx_get_hessian_groups)
   int n_star_bundles = 0;
   // STAR LEAVES (kernels.hip: front_star_leaf_kernel): the star variables whose clique is a lean leaf are eliminated
   // straight from [A b] by the factorization, and their H panels are not assembled — only their rhs rows are written (by
@@ -499,6 +500,7 @@ void sort_absolute_list(const HostProblem& P, std::vector<int>& list);
 void whiten_linear_factor(const HostProblem& P, int f, const double* src, double* J);
 gsx_status upload_problem(gsx_context* c);
 gsx_status upload_symbolic(gsx_context* c);
+void plan_hessian_groups(gsx_context* c);   // host only: hgroups, hv_*, h_star_bundles from the symbolic analysis
 void plan_backsolve(const Symbolic& S, std::vector<BsLaunch>& level_plan, std::vector<BsLaunch>& plan);
 // solver.hip: the device pipeline (all asynchronous up to readback) ...
 void launch_lds_group(const DevProblem& P, const DevSymbolic& S, const int* ids, const SmallLaunch& g, const double* H,

@@ -740,6 +740,8 @@ gsx_status gsx_set_ordering(gsx_handle h, const uint64_t* keys, int32_t n) {
     hipSetDevice(h->device);
     st = upload_symbolic(h);
     if (st != GSX_OK) return st;
+  } else {
+    plan_hessian_groups(h);   // (upload_symbolic makes this plan on a handle with a device: gsx_get_hessian_groups reads it)
   }
   return GSX_OK;
 }
@@ -864,6 +866,100 @@ gsx_status gsx_get_gather_plan(gsx_handle h, int32_t* n_segments, int64_t* n_sou
       combines[4 * i + 3] = S.gm_nslots[i];
     }
   return GSX_OK;
+}
+
+gsx_status gsx_get_hessian_groups(gsx_handle h, int32_t* classes, int32_t* group, int32_t* position, int32_t* bundle,
+                                  int32_t* bundle_size, int32_t* fused_diag_star) {
+  if (!h) return GSX_E_INVALID;
+  if (!h->has_symbolic) {
+    h->err = "ordering not set";
+    return GSX_E_STATE;
+  }
+  const int n = h->P.n_vars;
+  // star variable at position p of its group -> its bundle
+  std::vector<int> bundle_at;
+  for (size_t b = 0; b < h->h_star_bundles.size(); ++b) bundle_at.insert(bundle_at.end(), h->h_star_bundles[b].y, (int)b);
+  bool has_bundled_star = false, has_diag = false;
+  for (int v = 0; v < n; ++v) {
+    const int g = h->hv_group_of_var[v];
+    int cls = -1, pos = -1, bi = -1, bn = 0;
+    if (g >= 0) {
+      const gsx_context::HGroup& G = h->hgroups[g];
+      cls = G.threads == -2 ? GSX_H_TILE : G.threads == -1 ? GSX_H_STAR : G.threads == 0 ? GSX_H_DIAG
+            : G.global ? GSX_H_HUGE : G.threads == 64 ? GSX_H_LIGHT : GSX_H_HEAVY;
+      pos = h->hv_pos[v] - G.begin;
+      if (cls == GSX_H_STAR && pos < (int)bundle_at.size()) {   // (the bundles tile the group in order, or there are none)
+        bi = bundle_at[pos];
+        bn = h->h_star_bundles[bi].y;
+      }
+      has_bundled_star |= cls == GSX_H_STAR && h->n_star_bundles > 0;
+      has_diag |= cls == GSX_H_DIAG;
+    }
+    if (classes) classes[v] = cls;
+    if (group) group[v] = g;
+    if (position) position[v] = pos;
+    if (bundle) bundle[v] = bi;
+    if (bundle_size) bundle_size[v] = bn;
+  }
+  if (fused_diag_star) *fused_diag_star = has_bundled_star && has_diag && !h->fused_star;   // (dev_assemble_h)
+  return GSX_OK;
+}
+
+gsx_status gsx_get_hessian_panel(gsx_handle h, uint64_t key, int32_t* rows, int32_t* dim, double* out, int32_t* row_var,
+                                 int32_t* row_scalar) {
+  if (!h) return GSX_E_INVALID;
+  if (!h->has_symbolic) {
+    h->err = "ordering not set";
+    return GSX_E_STATE;
+  }
+  const HostProblem& P = h->P;
+  const Symbolic& S = h->S;
+  int v = -1;
+  for (int k = 0; k < P.n_vars && v < 0; ++k)
+    if (P.keys[k] == key) v = k;
+  if (v < 0) {
+    h->err = "no variable has this key";
+    return GSX_E_INVALID;
+  }
+  if (!S.scheduled[S.front_of_var[v]]) {
+    h->err = "the variable belongs to another rank's subtree: its panel is not assembled on this handle";
+    return GSX_E_STATE;
+  }
+  const int d = P.dims[v], nrows = S.h_rows[v];
+  if (rows) *rows = nrows;
+  if (dim) *dim = d;
+  if (!out) return GSX_OK;
+  gsx_status st = begin_call(h, true, true);
+  if (st != GSX_OK) return st;
+  if (!h->linearized) {
+    h->err = "linearize first";
+    return GSX_E_STATE;
+  }
+  if (row_var && row_scalar) {
+    // the panel's rows: the variable, its later-eliminated neighbours in elimination order, the right-hand side
+    std::vector<int> nb;
+    for (int f = 0; f < P.n_factors; ++f) {
+      bool has = false;
+      for (int q = P.f_key_ptr[f]; q < P.f_key_ptr[f + 1]; ++q) has |= P.f_vars[q] == v;
+      for (int q = P.f_key_ptr[f]; has && q < P.f_key_ptr[f + 1]; ++q)
+        if (S.pos[P.f_vars[q]] > S.pos[v]) nb.push_back(P.f_vars[q]);
+    }
+    std::sort(nb.begin(), nb.end(), [&](int a, int b) { return S.pos[a] < S.pos[b]; });
+    nb.erase(std::unique(nb.begin(), nb.end()), nb.end());
+    nb.insert(nb.begin(), v);
+    int r = 0;
+    for (int u : nb)
+      for (int k = 0; k < P.dims[u] && r < nrows - 1; ++k, ++r) row_var[r] = u, row_scalar[r] = k;
+    if (r != nrows - 1) {
+      h->err = "internal: the panel's rows are not those of the variable's later neighbours";
+      return GSX_E_INVALID;
+    }
+    row_var[r] = -1;
+    row_scalar[r] = 0;
+  }
+  if (!h->h_ready) dev_assemble_h(h);
+  dev_ensure_hstar(h);   // (the star leaves' panels: the factorization forms them in registers)
+  return download(h, h->d_H.p + S.h_off[v], out, (int64_t)nrows * d);
 }
 
 gsx_status gsx_scratch_buffer(gsx_handle h, double** device_ptr, int64_t* count) {

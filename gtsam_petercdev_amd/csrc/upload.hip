@@ -345,6 +345,135 @@ extern "C" int gsxtest_backsolve_plan(gsx_context* c, int which, int* out, int c
   return (int)recs.size();
 }
 
+// ---- H assembly groups: variables bucketed by panel size (LDS) and term count (host only: gsx_get_hessian_groups
+//      reads the plan, and makes it itself on a handle without a device) ----
+void plan_hessian_groups(gsx_context* c) {
+  const Symbolic& S = c->S;
+  const HostProblem& P = c->P;
+  struct VI {
+    int v, psize;
+    int64_t terms;
+  };
+  std::vector<VI> light, heavy, huge, diag, star, tile;
+  // a "tile" variable: at most 64 terms, all from NARROW factors (<= 16 columns with the rhs, <= 8 rows): one matrix-core
+  // product per factor (assemble_h_tile_kernel).  GSX_H_TILE_OFF keeps the generic kernel (measurements).
+  static const bool tile_off = std::getenv("GSX_H_TILE_OFF") != nullptr;
+  auto is_tile = [&](int v) {
+    const int64_t tb = S.term_ptr[v], te = S.term_ptr[v + 1];
+    if (tile_off || te - tb < 2 || te - tb > 64 || (int64_t)S.h_rows[v] * P.dims[v] * 8 * 4 > 48 * 1024) return false;
+    int64_t t = tb;
+    while (t < te) {
+      int64_t e = t + 1;
+      while (e < te && S.t_jac[e] == S.t_jac[t]) ++e;
+      // the factor's last term is its rhs term: column index = number of columns - 1
+      if (S.t_m[t] > 8 || S.t_dB[e - 1] != 1 || S.t_dst[e - 1] != S.h_rows[v] - 1 || S.t_colB[e - 1] + 1 > 16) return false;
+      t = e;
+    }
+    return true;
+  };
+  // a "star" variable: all its factors are binary with a later-eliminated partner, all of one shape (three terms
+  // each: own block, partner block, rhs — with equal rows, columns and partner dimension)
+  std::vector<int> star_dst;
+  auto is_star = [&](int v) {
+    const int64_t tb = S.term_ptr[v], te = S.term_ptr[v + 1];
+    if (te - tb < 3 || (te - tb) % 3 != 0 || P.dims[v] > 7) return false;
+    star_dst.clear();
+    for (int64_t t = tb; t < te; t += 3) {
+      star_dst.push_back(S.t_dst[t + 1]);
+      if (S.t_dst[t] != 0 || S.t_dst[t + 2] != S.h_rows[v] - 1 || S.t_dB[t + 2] != 1) return false;
+      if (S.t_dst[t + 1] == 0 || S.t_dst[t + 1] == S.h_rows[v] - 1) return false;
+      if (S.t_m[t] != S.t_m[tb] || S.t_colA[t] != S.t_colA[tb] || S.t_colB[t + 1] != S.t_colB[tb + 1] ||
+          S.t_dB[t + 1] != S.t_dB[tb + 1] || S.t_colB[t + 2] != S.t_colB[tb + 2] || S.t_jac[t] != S.t_jac[t + 1] ||
+          S.t_jac[t] != S.t_jac[t + 2])
+        return false;
+    }
+    // every partner block is written by exactly one factor (two factors to the same partner would have to be summed)
+    std::sort(star_dst.begin(), star_dst.end());
+    return std::adjacent_find(star_dst.begin(), star_dst.end()) == star_dst.end();
+  };
+  for (int v = 0; v < P.n_vars; ++v) {
+    if (!S.scheduled[S.front_of_var[v]]) continue;  // another rank's subtree
+    const int psize = S.h_rows[v] * P.dims[v];
+    const int64_t terms = S.term_ptr[v + 1] - S.term_ptr[v];
+    if (is_star(v)) {
+      star.push_back({v, psize, terms});
+      continue;
+    }
+    // no later neighbour through any factor (panel = own block + rhs) and many factors: the matrix-core kernel
+    if (terms >= 64 && S.h_rows[v] == P.dims[v] + 1 && P.dims[v] <= 15) diag.push_back({v, psize, terms});
+    else if (is_tile(v)) tile.push_back({v, psize, terms});
+    else if (terms >= 96 && (int64_t)psize * 4 * 8 <= 48 * 1024) heavy.push_back({v, psize, terms});
+    else if ((int64_t)psize * 8 <= 48 * 1024) light.push_back({v, psize, terms});
+    else huge.push_back({v, psize, terms});
+  }
+  auto by_psize = [](const VI& a, const VI& b) { return a.psize < b.psize; };
+  std::stable_sort(light.begin(), light.end(), by_psize);
+  std::stable_sort(heavy.begin(), heavy.end(), by_psize);
+  std::vector<int> hv;
+  c->hgroups.clear();
+  auto emit = [&](std::vector<VI>& L, int threads, int copies, bool global) {
+    size_t i = 0;
+    while (i < L.size()) {
+      // group = run whose largest panel is at most 2x (and at least 1 KB) of its smallest
+      size_t j = i;
+      const int lo = std::max(L[i].psize, 128);
+      while (j < L.size() && L[j].psize <= 2 * lo) ++j;
+      const int maxp = L[j - 1].psize;
+      c->hgroups.push_back({(int)hv.size(), (int)(j - i), threads, global ? 0 : maxp * copies * 8, global});
+      for (size_t k = i; k < j; ++k) hv.push_back(L[k].v);
+      i = j;
+    }
+  };
+  std::stable_sort(tile.begin(), tile.end(), by_psize);
+  emit(tile, -2, 4, false);   // (four waves a workgroup, a panel each)
+  emit(light, 64, 1, false);
+  emit(heavy, 256, 4, false);
+  emit(huge, 64, 1, true);
+  c->n_star_bundles = 0;
+  c->h_star_bundles.clear();
+  if (!star.empty()) {  // threads == -1 marks the group
+    c->hgroups.push_back({(int)hv.size(), (int)star.size(), -1, 0, false});
+    for (const VI& x : star) hv.push_back(x.v);
+    // bundles for the one-wave-per-bundle kernel: consecutive variables of one shape, <= 5 of them (the own entries of
+    // a bundle fit a wave: 5 x (3*3 + 3) lanes), <= 64 factors; a variable too big or of another shape is alone
+    auto shape = [&](int v) {
+      const int64_t t = S.term_ptr[v];
+      return std::array<int, 6>{P.dims[v], S.t_m[t], S.t_colA[t], S.t_colB[t + 1], S.t_dB[t + 1], S.t_colB[t + 2]};
+    };
+    std::vector<int2>& bundles = c->h_star_bundles;
+    size_t i = 0;
+    while (i < star.size()) {
+      const auto sh = shape(star[i].v);
+      const int nown = sh[0] * sh[0] + sh[0];
+      int nf = (int)(star[i].terms / 3), nv = 1;
+      if (nf > 64 || nown > 64) {  // (the bundle kernel holds a factor per lane)
+        bundles.clear();
+        break;
+      }
+      while (i + nv < star.size() && nv < 5 && (nv + 1) * nown <= 64 && shape(star[i + nv].v) == sh &&
+             nf + (int)(star[i + nv].terms / 3) <= 64) {
+        nf += (int)(star[i + nv].terms / 3);
+        ++nv;
+      }
+      bundles.push_back(int2{(int)i, nv});
+      i += nv;
+    }
+    c->n_star_bundles = (int)bundles.size();
+  }
+  if (!diag.empty()) {  // threads == 0 marks the group for launch_assemble_h_group
+    c->hgroups.push_back({(int)hv.size(), (int)diag.size(), 0, 0, false});
+    for (const VI& x : diag) hv.push_back(x.v);
+  }
+  c->hv_list = hv;
+  c->hv_group_of_var.assign(P.n_vars, -1);
+  c->hv_pos.assign(P.n_vars, -1);
+  for (size_t g = 0; g < c->hgroups.size(); ++g)
+    for (int k = c->hgroups[g].begin; k < c->hgroups[g].begin + c->hgroups[g].count; ++k) {
+      c->hv_group_of_var[hv[k]] = (int)g;
+      c->hv_pos[hv[k]] = k;
+    }
+}
+
 // Build the launch plan (host) and upload the symbolic tables.
 gsx_status upload_symbolic(gsx_context* c) {
   const Symbolic& S = c->S;
@@ -462,132 +591,9 @@ gsx_status upload_symbolic(gsx_context* c) {
   }
   HIPCHK(c, c->d_H.alloc(std::max<int64_t>(S.h_size, 1)));
   HIPCHK(c, c->d_arena.alloc(std::max<int64_t>(S.arena_size, 1)));
-  // ---- H assembly groups: variables bucketed by panel size (LDS) and term count -----------------
-  {
-    struct VI {
-      int v, psize;
-      int64_t terms;
-    };
-    std::vector<VI> light, heavy, huge, diag, star, tile;
-    // a "tile" variable: at most 64 terms, all from NARROW factors (<= 16 columns with the rhs, <= 8 rows): one matrix-core
-    // product per factor (assemble_h_tile_kernel).  GSX_H_TILE_OFF keeps the generic kernel (measurements).
-    static const bool tile_off = std::getenv("GSX_H_TILE_OFF") != nullptr;
-    auto is_tile = [&](int v) {
-      const int64_t tb = S.term_ptr[v], te = S.term_ptr[v + 1];
-      if (tile_off || te - tb < 2 || te - tb > 64 || (int64_t)S.h_rows[v] * P.dims[v] * 8 * 4 > 48 * 1024) return false;
-      int64_t t = tb;
-      while (t < te) {
-        int64_t e = t + 1;
-        while (e < te && S.t_jac[e] == S.t_jac[t]) ++e;
-        // the factor's last term is its rhs term: column index = number of columns - 1
-        if (S.t_m[t] > 8 || S.t_dB[e - 1] != 1 || S.t_dst[e - 1] != S.h_rows[v] - 1 || S.t_colB[e - 1] + 1 > 16) return false;
-        t = e;
-      }
-      return true;
-    };
-    // a "star" variable: all its factors are binary with a later-eliminated partner, all of one shape (three terms
-    // each: own block, partner block, rhs — with equal rows, columns and partner dimension)
-    std::vector<int> star_dst;
-    auto is_star = [&](int v) {
-      const int64_t tb = S.term_ptr[v], te = S.term_ptr[v + 1];
-      if (te - tb < 3 || (te - tb) % 3 != 0 || P.dims[v] > 7) return false;
-      star_dst.clear();
-      for (int64_t t = tb; t < te; t += 3) {
-        star_dst.push_back(S.t_dst[t + 1]);
-        if (S.t_dst[t] != 0 || S.t_dst[t + 2] != S.h_rows[v] - 1 || S.t_dB[t + 2] != 1) return false;
-        if (S.t_dst[t + 1] == 0 || S.t_dst[t + 1] == S.h_rows[v] - 1) return false;
-        if (S.t_m[t] != S.t_m[tb] || S.t_colA[t] != S.t_colA[tb] || S.t_colB[t + 1] != S.t_colB[tb + 1] ||
-            S.t_dB[t + 1] != S.t_dB[tb + 1] || S.t_colB[t + 2] != S.t_colB[tb + 2] || S.t_jac[t] != S.t_jac[t + 1] ||
-            S.t_jac[t] != S.t_jac[t + 2])
-          return false;
-      }
-      // every partner block is written by exactly one factor (two factors to the same partner would have to be summed)
-      std::sort(star_dst.begin(), star_dst.end());
-      return std::adjacent_find(star_dst.begin(), star_dst.end()) == star_dst.end();
-    };
-    for (int v = 0; v < P.n_vars; ++v) {
-      if (!S.scheduled[S.front_of_var[v]]) continue;  // another rank's subtree
-      const int psize = S.h_rows[v] * P.dims[v];
-      const int64_t terms = S.term_ptr[v + 1] - S.term_ptr[v];
-      if (is_star(v)) {
-        star.push_back({v, psize, terms});
-        continue;
-      }
-      // no later neighbour through any factor (panel = own block + rhs) and many factors: the matrix-core kernel
-      if (terms >= 64 && S.h_rows[v] == P.dims[v] + 1 && P.dims[v] <= 15) diag.push_back({v, psize, terms});
-      else if (is_tile(v)) tile.push_back({v, psize, terms});
-      else if (terms >= 96 && (int64_t)psize * 4 * 8 <= 48 * 1024) heavy.push_back({v, psize, terms});
-      else if ((int64_t)psize * 8 <= 48 * 1024) light.push_back({v, psize, terms});
-      else huge.push_back({v, psize, terms});
-    }
-    auto by_psize = [](const VI& a, const VI& b) { return a.psize < b.psize; };
-    std::stable_sort(light.begin(), light.end(), by_psize);
-    std::stable_sort(heavy.begin(), heavy.end(), by_psize);
-    std::vector<int> hv;
-    c->hgroups.clear();
-    auto emit = [&](std::vector<VI>& L, int threads, int copies, bool global) {
-      size_t i = 0;
-      while (i < L.size()) {
-        // group = run whose largest panel is at most 2x (and at least 1 KB) of its smallest
-        size_t j = i;
-        const int lo = std::max(L[i].psize, 128);
-        while (j < L.size() && L[j].psize <= 2 * lo) ++j;
-        const int maxp = L[j - 1].psize;
-        c->hgroups.push_back({(int)hv.size(), (int)(j - i), threads, global ? 0 : maxp * copies * 8, global});
-        for (size_t k = i; k < j; ++k) hv.push_back(L[k].v);
-        i = j;
-      }
-    };
-    std::stable_sort(tile.begin(), tile.end(), by_psize);
-    emit(tile, -2, 4, false);   // (four waves a workgroup, a panel each)
-    emit(light, 64, 1, false);
-    emit(heavy, 256, 4, false);
-    emit(huge, 64, 1, true);
-    c->n_star_bundles = 0;
-    if (!star.empty()) {  // threads == -1 marks the group
-      c->hgroups.push_back({(int)hv.size(), (int)star.size(), -1, 0, false});
-      for (const VI& x : star) hv.push_back(x.v);
-      // bundles for the one-wave-per-bundle kernel: consecutive variables of one shape, <= 5 of them (the own entries of
-      // a bundle fit a wave: 5 x (3*3 + 3) lanes), <= 64 factors; a variable too big or of another shape is alone
-      auto shape = [&](int v) {
-        const int64_t t = S.term_ptr[v];
-        return std::array<int, 6>{P.dims[v], S.t_m[t], S.t_colA[t], S.t_colB[t + 1], S.t_dB[t + 1], S.t_colB[t + 2]};
-      };
-      std::vector<int2> bundles;
-      size_t i = 0;
-      while (i < star.size()) {
-        const auto sh = shape(star[i].v);
-        const int nown = sh[0] * sh[0] + sh[0];
-        int nf = (int)(star[i].terms / 3), nv = 1;
-        if (nf > 64 || nown > 64) {  // (the bundle kernel holds a factor per lane)
-          bundles.clear();
-          break;
-        }
-        while (i + nv < star.size() && nv < 5 && (nv + 1) * nown <= 64 && shape(star[i + nv].v) == sh &&
-               nf + (int)(star[i + nv].terms / 3) <= 64) {
-          nf += (int)(star[i + nv].terms / 3);
-          ++nv;
-        }
-        bundles.push_back(int2{(int)i, nv});
-        i += nv;
-      }
-      c->n_star_bundles = (int)bundles.size();
-      if (c->n_star_bundles) HIPCHK(c, c->d_star_bundles.upload(bundles, st));
-    }
-    if (!diag.empty()) {  // threads == 0 marks the group for launch_assemble_h_group
-      c->hgroups.push_back({(int)hv.size(), (int)diag.size(), 0, 0, false});
-      for (const VI& x : diag) hv.push_back(x.v);
-    }
-    c->hv_list = hv;
-    c->hv_group_of_var.assign(P.n_vars, -1);
-    c->hv_pos.assign(P.n_vars, -1);
-    for (size_t g = 0; g < c->hgroups.size(); ++g)
-      for (int k = c->hgroups[g].begin; k < c->hgroups[g].begin + c->hgroups[g].count; ++k) {
-        c->hv_group_of_var[hv[k]] = (int)g;
-        c->hv_pos[hv[k]] = k;
-      }
-    HIPCHK(c, c->d_hvars.upload(hv, st));
-  }
+  plan_hessian_groups(c);
+  if (c->n_star_bundles) HIPCHK(c, c->d_star_bundles.upload(c->h_star_bundles, st));
+  HIPCHK(c, c->d_hvars.upload(c->hv_list, st));
   // ---- factorization launch plan ---------------------------------------------------------------------
   c->small_launch.assign(S.n_levels, {});
   c->big_descs.clear();

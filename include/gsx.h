@@ -522,6 +522,43 @@ gsx_status gsx_get_front_classes(gsx_handle h, int32_t* classes);
  *                        partial sums the combine pass adds in slot order */
 gsx_status gsx_get_gather_plan(gsx_handle h, int32_t* n_segments, int64_t* n_sources, int32_t* n_combines,
                                int64_t* segments, int32_t* sources, int32_t* combines);
+/* Which kernel assembles the H panel (J'J, J'b) of every variable of the current tree, read-only and host side (answers
+ * on a handle without a device, and never touches one).  Arrays of n_vars entries indexed as in gsx_get_tree; any may be
+ * NULL:
+ *   classes[v]      GSX_H_TILE   2..64 terms, every factor at most 8 rows and 16 columns with the rhs: one matrix-core
+ *                                product per factor, a wave per panel, four panels a workgroup
+ *                   GSX_H_LIGHT  panel of at most 6144 doubles, fewer than 96 terms: one wave, one LDS copy
+ *                   GSX_H_HEAVY  panel of at most 1536 doubles, 96 terms or more: four waves, an LDS copy each, summed
+ *                                in wave order
+ *                   GSX_H_HUGE   panel above 6144 doubles: one wave straight into global memory
+ *                   GSX_H_STAR   dimension at most 7, every factor binary (three terms) with a later-eliminated partner
+ *                                of its own, all factors of one shape
+ *                   GSX_H_DIAG   no later neighbour, dimension at most 15, 64 terms (32 factors) or more: matrix cores,
+ *                                four waves
+ *                   -1           the variable belongs to another rank's subtree (gsx_set_shard)
+ *                   (a term = one block product of one factor: own block, one per later neighbour in the factor, rhs)
+ *   group[v]        index of the variable's launch group (panels of like size share a launch), -1 with class -1
+ *   position[v]     its place in the group's variable list
+ *   bundle[v], bundle_size[v]   a star variable: the bundle (one wave) it shares with up to four neighbours of its
+ *                   shape, and how many variables the bundle holds; -1 and 0 when the star group runs unbundled (one
+ *                   variable has more than 64 factors) and for every other class
+ *   *fused_diag_star   1 when the star bundles and the diag group run in one launch.  A handle that eliminates star
+ *                   leaves straight from [A b] (the default when the tree has some; not GSX_FUSED_STAR=0, not a handle
+ *                   without a device) launches the two apart: 0. */
+enum { GSX_H_TILE = 0, GSX_H_LIGHT = 1, GSX_H_HEAVY = 2, GSX_H_HUGE = 3, GSX_H_STAR = 4, GSX_H_DIAG = 5 };
+gsx_status gsx_get_hessian_groups(gsx_handle h, int32_t* classes, int32_t* group, int32_t* position, int32_t* bundle,
+                                  int32_t* bundle_size, int32_t* fused_diag_star);
+/* The H panel of variable `key` as the device assembled it from the current [A b] blocks: *rows x *dim doubles,
+ * column-major (entry (i, j) at out[i + j * *rows]); rows = the variable's own scalars, then those of its
+ * later-eliminated neighbours in elimination order, then the right-hand side; entry (i, j) = sum over the variable's
+ * factors of column i of the row's block times column j of the variable's block (the last row: b' A).  row_var[i],
+ * row_scalar[i] name the variable (index as in gsx_get_tree; -1: the right-hand side) and the scalar of row i; both may
+ * be NULL.  out = NULL queries *rows and *dim only (host side).  Like gsx_hessian_diagonal the call assembles stale
+ * panels first, those of the star leaves included, which the factorization otherwise forms in registers and never
+ * stores.  GSX_E_STATE before gsx_linearize and for a variable of another rank's subtree; on a sharded handle a cap
+ * variable's panel holds this rank's terms only. */
+gsx_status gsx_get_hessian_panel(gsx_handle h, uint64_t key, int32_t* rows, int32_t* dim, double* out, int32_t* row_var,
+                                 int32_t* row_scalar);
 gsx_status gsx_get_ordering(gsx_handle h, uint64_t* keys_out);
 /* Bayes-tree structure for parity checks: per front the frontal / separator
  * variable indices (CSR) and the parent front (-1 = root).  Pass NULL arrays to

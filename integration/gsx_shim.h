@@ -323,6 +323,25 @@ inline gtsam::Values unpack_values(const gtsam::Values& like, const std::vector<
   return out;
 }
 
+// Diagnostics (read-only): which kernel assembles every variable's H panel (gsx_get_hessian_groups; class per variable in
+// the handle's variable order, GSX_H_TILE ... GSX_H_DIAG) and one panel as the device assembled it (gsx_get_hessian_panel:
+// rows = the variable, its later-eliminated neighbours, the right-hand side).
+inline std::vector<int32_t> hessian_classes(gsx_handle h, size_t n_vars, bool* fused_diag_star = nullptr) {
+  std::vector<int32_t> cls(std::max<size_t>(n_vars, 1), -1);
+  int32_t fused = 0;
+  check(gsx_get_hessian_groups(h, cls.data(), nullptr, nullptr, nullptr, nullptr, &fused), h, "gsx_get_hessian_groups");
+  if (fused_diag_star) *fused_diag_star = fused != 0;
+  cls.resize(n_vars);
+  return cls;
+}
+inline gtsam::Matrix hessian_panel(gsx_handle h, gtsam::Key key) {
+  int32_t rows = 0, dim = 0;
+  check(gsx_get_hessian_panel(h, key, &rows, &dim, nullptr, nullptr, nullptr), h, "gsx_get_hessian_panel");
+  gtsam::Matrix panel(rows, dim);   // (column-major, as the call writes it)
+  check(gsx_get_hessian_panel(h, key, &rows, &dim, panel.data(), nullptr, nullptr), h, "gsx_get_hessian_panel");
+  return panel;
+}
+
 inline gsx_lm_params lower_params(const gtsam::LevenbergMarquardtParams& p) {
   gsx_lm_params q;
   q.max_iterations = (int32_t)p.maxIterations, q.relative_error_tol = p.relativeErrorTol, q.absolute_error_tol = p.absoluteErrorTol;

@@ -144,6 +144,12 @@ def _root(be):
     return max(f for f, p in enumerate(parent) if p < 0)
 
 
+def _groups(be):
+    """gsx_get_hessian_groups as one array (host side: it answers in every state that has an ordering)."""
+    g = be.hessian_groups()
+    return np.concatenate([g[k] for k in ("class", "group", "position", "bundle", "bundle_size")] + [[int(g["fused_diag_star"])]])
+
+
 READERS = [
     ("get_jacobians", lambda be, g: be.jacobians()),
     ("hessian_diagonal", lambda be, g: be.hessian_diagonal()),
@@ -155,6 +161,8 @@ READERS = [
     ("get_conditional_root", lambda be, g: be.conditional(_root(be))),
     ("linear_error", lambda be, g: np.array(be.linear_error())),
     ("retract_no_delta", lambda be, g: np.array([be.retract(None, commit=False)])),
+    ("get_hessian_groups", lambda be, g: _groups(be)),
+    ("get_hessian_panel", lambda be, g: np.concatenate([a.ravel() for a in be.hessian_panel(g.key)])),
 ]
 
 
@@ -189,10 +197,10 @@ EVENTS = {
     "update_one_factor": _update,
 }
 
-#              jac      hdiag    solve 0  solve l  wildfire relin    marginal cond     lin.err  retract
-_MOVED = ("state", "state", "state", "state", "state", "state", "ok", "old", "state", "state")
-_BLOCKS = ("ok", "ok", "ok", "ok", "state", "state", "ok", "state", "state", "state")
-_ALL_OK = ("ok",) * 10
+#              jac      hdiag    solve 0  solve l  wildfire relin    marginal cond     lin.err  retract  h.groups h.panel
+_MOVED = ("state", "state", "state", "state", "state", "state", "ok", "old", "state", "state", "ok", "state")
+_BLOCKS = ("ok", "ok", "ok", "ok", "state", "state", "ok", "state", "state", "state", "ok", "ok")
+_ALL_OK = ("ok",) * 12
 TABLE = {
     # the values moved, the arena was left alone: everything asks for a linearization, the marginal makes its own, and
     # the conditional is the previous linearization's
@@ -201,22 +209,23 @@ TABLE = {
     "gn_iteration": _MOVED,        # (its factorization is that of the linearization at the values it started from)
     "dogleg_iteration": _MOVED,
     # LM drops the factorization with the values it accepted
-    "lm_iteration_accepted": ("state", "state", "state", "state", "state", "state", "ok", "state", "state", "state"),
+    "lm_iteration_accepted": ("state", "state", "state", "state", "state", "state", "ok", "state", "state", "state", "ok",
+                              "state"),
     # a damped factorization and its step are resident: no undamped one for the wildfire pass / the partial update
-    "lm_trial_rejected": ("ok", "ok", "ok", "ok", "state", "state", "ok", "trial", "trial", "trial"),
+    "lm_trial_rejected": ("ok", "ok", "ok", "ok", "state", "state", "ok", "trial", "trial", "trial", "ok", "ok"),
     # new blocks / a new tree / a new graph under the same linearization point: linearized, nothing else
     "set_block_jacobians": _BLOCKS,
     "set_ordering": _BLOCKS,
     "update_one_factor": _BLOCKS,
     # the factorization is current, its back-substitution is not
-    "relinearize_partial_moved": ("ok", "ok", "ok", "ok", "ok", "ok", "ok", "ok", "state", "state"),
+    "relinearize_partial_moved": ("ok", "ok", "ok", "ok", "ok", "ok", "ok", "ok", "state", "state", "ok", "ok"),
 }
 # a PCG handle factors nothing in its drivers: the linearize of the iteration / trial drops the resident factorization
 # and no new one arrives; Dogleg refuses the handle and leaves it as it was
 TABLE_PCG = dict(TABLE)
 TABLE_PCG["gn_iteration"] = _MOVED[:7] + ("state",) + _MOVED[8:]
 TABLE_PCG["dogleg_iteration"] = _ALL_OK
-TABLE_PCG["lm_trial_rejected"] = ("ok", "ok", "ok", "ok", "state", "state", "ok", "state", "trial", "trial")
+TABLE_PCG["lm_trial_rejected"] = ("ok", "ok", "ok", "ok", "state", "state", "ok", "state", "trial", "trial", "ok", "ok")
 EVENT_STATUS_PCG = {"dogleg_iteration": A.GSX_E_STATE}
 
 
@@ -287,8 +296,8 @@ def test_readers_after_event(gpu, name, event):
         before.close()
 
 
-#                   jac   hdiag solve 0  solve l wildfire relin    marginal cond     lin.err  retract
-ROW_FAILED = ("ok", "ok", "indet", "ok", "state", "state", "indet", "state", "state", "state")
+#                   jac   hdiag solve 0  solve l wildfire relin    marginal cond     lin.err  retract  h.groups h.panel
+ROW_FAILED = ("ok", "ok", "indet", "ok", "state", "state", "indet", "state", "state", "state", "ok", "ok")
 
 
 def test_readers_after_a_failed_factorization(gpu):

@@ -307,12 +307,14 @@ def selfcal(n_poses, n_points):
     return _cache[key]
 
 
-def steps_against_dense(arr, what, ordering):
+def steps_against_dense(arr, what, ordering, check_groups=None):
     be = backend(arr)
     if not isinstance(ordering, int):
         be.set_ordering(ordering)
     elif ordering != A.ORDER_MINDEGREE:
         be.set_ordering(be.compute_ordering(ordering))
+    if check_groups is not None:   # which assembly kernel every variable goes to, from the handle that is judged
+        check_groups(be.hessian_groups()["class"])
     be.linearize()
     J, b = S.dense_system(arr, arr.values)
     H, g = J.T @ J, J.T @ b
@@ -331,28 +333,66 @@ def steps_against_dense(arr, what, ordering):
     be.close()
 
 
-@pytest.mark.parametrize("order", ["schur", "mindegree", "K first"])
+@pytest.mark.parametrize("order", ["schur", "mindegree", "K first", "K last"])
 @pytest.mark.parametrize("shape", [(6, 5), (8, 8), (12, 20)])
 def test_sfm2_steps_match_a_dense_solve_in_every_assembly_class(shape, order):
     """Steps at lambda 0, 1e-3 and 10, with and without diagonal damping, against the dense solve.  K eliminated last has two
     term records per factor (own block, rhs): 6 x 5 gives it 27 observations + its prior = 56 records (below 64: a tile /
-    light variable), 8 x 8 gives 116 and 12 x 20 gives 452 (above: a diag variable).  With K ordered first every landmark's
-    and pose's term list has the three-per-factor shape of a binary factor (own, partner, rhs, at columns 6 / 0 / 14).
-    gsx_get_front_classes / gsx_get_stats tell the elimination class of the fronts, not the H-assembly group of a variable:
-    what they tell is printed and its consistency asserted."""
+    light variable), 8 x 8 gives 116 and 12 x 20 gives 452 (above: a diag variable).  With K ordered first a landmark or
+    pose whose factors all have a later partner has the three-per-factor term list of a binary factor (own, partner, rhs,
+    at columns 6 / 0 / 14): a star variable.
+    gsx_get_hessian_groups now says where the variables went, and it is asserted.  It also showed what this test could only
+    hope before: neither the Schur nor the minimum-degree ordering eliminates K last (K keeps later neighbours, so at
+    8 x 8 and 12 x 20 it is a heavy variable there, never a diag one), hence the fourth ordering "K last"; and with K first
+    only the variables eliminated before all their partners are star, the others are tile variables.
+    gsx_get_front_classes / gsx_get_stats tell the elimination class of the fronts; what they tell is printed and its
+    consistency asserted."""
     arr = selfcal(*shape)
     n_obs = int((arr.f_type == S.F_SFM2).sum())
     n_p, n_l = shape
     assert n_obs == (n_l - 2) * n_p + 3 + 6 and n_p >= 6
-    if order == "K first":
+    kv = arr.n_vars - 1
+    is_pose = arr.var_types != A.VAR_VECTOR
+    is_lm = ~is_pose
+    is_lm[kv] = False
+
+    def check(cls):
+        names = [A.HESSIAN_CLASS_NAMES[c] for c in cls]
+        print(f"assembly classes {n_p} x {n_l}, {order}: K {names[kv]}, landmarks {sorted(set(np.array(names)[is_lm]))}, "
+              f"poses {sorted(set(np.array(names)[is_pose]))}")
+        assert np.all(cls >= 0)
+        if order == "K last":
+            assert (names[kv] == "diag") if shape != (6, 5) else (names[kv] in ("tile", "light"))
+        elif order == "K first":
+            assert names[kv] in ("tile", "light", "heavy")
+            # star: exactly the variables eliminated before all their partners (own, partner, rhs per factor, every
+            # factor an observation with a partner of its own); the others are tile variables
+            pos = {int(k): i for i, k in enumerate(ordering)}
+            pv = np.array([pos[int(k)] for k in arr.var_keys])
+            want = np.zeros(arr.n_vars, bool)
+            for v in np.flatnonzero(is_pose | is_lm):
+                later = [[int(u) for u in arr.f_vars[arr.f_key_ptr[f]:arr.f_key_ptr[f + 1]] if pv[u] > pv[v]]
+                         for f in range(arr.n_factors) if v in arr.f_vars[arr.f_key_ptr[f]:arr.f_key_ptr[f + 1]]]
+                partners = [l[0] for l in later if len(l) == 1]
+                want[v] = len(partners) == len(later) > 0 and len(set(partners)) == len(partners)
+            assert np.any(want) and not np.all(want[is_pose | is_lm])
+            assert np.array_equal(cls[is_pose | is_lm] == A.H_STAR, want[is_pose | is_lm]), (cls, want)
+            assert set(cls[is_pose | is_lm]) <= {A.H_STAR, A.H_TILE}
+        elif shape == (6, 5):
+            assert names[kv] in ("tile", "light")
+        else:
+            assert names[kv] == "heavy"                               # (not last: it has later neighbours)
+
+    if order in ("K first", "K last"):
         be = backend(arr)
         keys = [int(k) for k in be.compute_ordering(A.ORDER_SCHUR)]
         be.close()
         kk = int(arr.var_keys[-1])
-        ordering = [kk] + [k for k in keys if k != kk]
+        rest = [k for k in keys if k != kk]
+        ordering = [kk] + rest if order == "K first" else rest + [kk]
     else:
         ordering = A.ORDER_SCHUR if order == "schur" else A.ORDER_MINDEGREE
-    steps_against_dense(arr, f"self-calibration {n_p} x {n_l}, {order}", ordering)
+    steps_against_dense(arr, f"self-calibration {n_p} x {n_l}, {order}", ordering, check)
 
 
 # ---- 6. rig equivalence ------------------------------------------------------------------------------------------------
