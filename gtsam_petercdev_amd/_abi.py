@@ -16,12 +16,14 @@ import numpy as np
 
 # ---- enums (include/gsx.h) -------------------------------------------------
 GSX_OK, GSX_E_INVALID, GSX_E_NO_DEVICE, GSX_E_BAD_ORDERING, GSX_E_INDETERMINATE, GSX_E_STATE, GSX_E_NOMEM = range(7)
-VAR_VECTOR, VAR_POSE2, VAR_POSE3, VAR_CAMERA, VAR_ROT3 = range(5)
+VAR_VECTOR, VAR_POSE2, VAR_POSE3, VAR_CAMERA, VAR_ROT3, VAR_UNIT3, VAR_ESSENTIAL = range(7)
 F_LINEAR, F_PRIOR, F_BETWEEN, F_SFM, F_PROJECTION, F_BEARINGRANGE, F_RANGE, F_BEARING, F_STEREO, F_SFM2 = range(10)
 F_SMART_PROJECTION = 10
 F_TRANSLATION, F_BILINEAR_TRANSLATION = 11, 12   # gtsam/sfm/TranslationFactor.h
 # absolute-measurement factors: gtsam/navigation/{GPSFactor,AttitudeFactor,MagFactor,MagPoseFactor}.h, gtsam/slam/Pose*Prior.h
 F_GPS, F_POSE_TRANSLATION_PRIOR, F_POSE_ROTATION_PRIOR, F_ATTITUDE, F_MAG = 13, 14, 15, 16, 17
+# two-view geometry: gtsam/slam/EssentialMatrixFactor.h (1; 2 and 3; 4<Cal3_S2>), gtsam/slam/EssentialMatrixConstraint.h
+F_ESSENTIAL, F_ESSENTIAL_DEPTH, F_ESSENTIAL_CALIB, F_ESSENTIAL_CONSTRAINT = 18, 19, 20, 21
 MFAS_MAX_NODES = 8192    # GSX_MFAS_MAX_NODES
 SMART_MEAS_HEAD = 11   # doubles of a smart factor's meas before body_P_sensor / the pixels (include/gsx.h)
 NOISE_FORMAT_G2O, NOISE_FORMAT_TORO, NOISE_FORMAT_GRAPH, NOISE_FORMAT_COV, NOISE_FORMAT_AUTO = range(5)
@@ -37,8 +39,8 @@ GATHER_COMBINE_FIELDS = ("group", "task", "slot0", "nslots")
 H_TILE, H_LIGHT, H_HEAVY, H_HUGE, H_STAR, H_DIAG = range(6)
 HESSIAN_CLASS_NAMES = ("tile", "light", "heavy", "huge", "star", "diag")
 
-STATE_DIM = {VAR_POSE2: 3, VAR_POSE3: 12, VAR_CAMERA: 17, VAR_ROT3: 9}
-TANGENT_DIM = {VAR_POSE2: 3, VAR_POSE3: 6, VAR_CAMERA: 9, VAR_ROT3: 3}
+STATE_DIM = {VAR_POSE2: 3, VAR_POSE3: 12, VAR_CAMERA: 17, VAR_ROT3: 9, VAR_UNIT3: 3, VAR_ESSENTIAL: 12}
+TANGENT_DIM = {VAR_POSE2: 3, VAR_POSE3: 6, VAR_CAMERA: 9, VAR_ROT3: 3, VAR_UNIT3: 2, VAR_ESSENTIAL: 5}
 
 _STATUS_NAMES = {
     GSX_OK: "GSX_OK", GSX_E_INVALID: "GSX_E_INVALID", GSX_E_NO_DEVICE: "GSX_E_NO_DEVICE",
@@ -251,6 +253,8 @@ class ProblemArrays:
         sd[self.var_types == VAR_POSE3] = 12
         sd[self.var_types == VAR_CAMERA] = 17
         sd[self.var_types == VAR_ROT3] = 9
+        sd[self.var_types == VAR_UNIT3] = 3
+        sd[self.var_types == VAR_ESSENTIAL] = 12
         return sd
 
     def state_offsets(self) -> np.ndarray:

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/gsx.h"
+#include "unit3_math.h"
 
 struct gsx_context;
 // what gsx_dataset_get hands out (io.cpp: the file readers; translation_graph.cpp: gsx_translation_recovery_problem)
@@ -48,6 +49,8 @@ struct HostProblem {
   // device they are rows of sigma 1 / sqrt(mu) (problem.cpp) that the factorization eliminates by constraint pivots
   std::vector<int> con_factor, con_row;
   std::vector<double> con_mu;
+  // the variables whose state holds a unit direction (GSX_VAR_UNIT3, GSX_VAR_ESSENTIAL): empty for every other graph
+  std::vector<int> direction_vars;
 };
 
 // Symbolic factorization for one ordering.
@@ -175,32 +178,46 @@ struct Symbolic {
   int64_t max_F = 0, max_rows = 0, n_small = 0, n_big = 0, n_medium = 0;
 };
 
+// a variable whose state holds a unit direction: its type's name, and whether the direction in `state` is of unit length
+// (unit3_math.h: to 1e-9).  The one place that knows where the direction sits
+inline bool is_direction_type(int t) { return t == GSX_VAR_UNIT3 || t == GSX_VAR_ESSENTIAL; }
+inline const char* direction_type_name(int t) { return t == GSX_VAR_UNIT3 ? "GSX_VAR_UNIT3" : "GSX_VAR_ESSENTIAL"; }
+inline bool direction_state_ok(int t, const double* state) { return unit3_is_unit(state + (t == GSX_VAR_ESSENTIAL ? 9 : 0)); }
+
 // The refusal line of a call that has no handle (the writers, the initializers, triangulation): gsx_last_error(NULL)
 // returns the calling thread's last one.
 inline std::string& call_error() {
   static thread_local std::string e;
   return e;
 }
-// those calls read states by their own rules and know no Rot3: a description that holds a GSX_VAR_ROT3 variable is refused
-inline gsx_status refuse_rot3(const gsx_problem_desc* d, const char* who) {
+// those calls read states by their own rules and know no Rot3, Unit3 or EssentialMatrix: a description that holds a variable
+// of one of these types is refused by name
+inline gsx_status refuse_manifold_only_vars(const gsx_problem_desc* d, const char* who) {
   if (d && d->var_types)
-    for (int v = 0; v < d->n_vars; ++v)
-      if (d->var_types[v] == GSX_VAR_ROT3) {
+    for (int v = 0; v < d->n_vars; ++v) {
+      const int t = d->var_types[v];
+      if (t == GSX_VAR_ROT3 || is_direction_type(t)) {
         call_error() = std::string(who) + ": variable " + std::to_string(v) + " (key " +
-                       std::to_string(d->var_keys ? (unsigned long long)d->var_keys[v] : 0ull) + ") is a GSX_VAR_ROT3";
+                       std::to_string(d->var_keys ? (unsigned long long)d->var_keys[v] : 0ull) + ") is a " +
+                       (t == GSX_VAR_ROT3 ? "GSX_VAR_ROT3" : direction_type_name(t));
         return GSX_E_INVALID;
       }
+    }
   return GSX_OK;
 }
 
-// entry of a handle-less call that takes a description: the line of an earlier refusal goes, a Rot3 is refused by name
+// entry of a handle-less call that takes a description: the line of an earlier refusal goes, a Rot3, Unit3 or
+// EssentialMatrix variable is refused by name
 inline gsx_status enter_call(const gsx_problem_desc* d, const char* who) {
   call_error().clear();
-  return refuse_rot3(d, who);
+  return refuse_manifold_only_vars(d, who);
 }
 
 // host algorithms
 gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string& err);
+// the directions of the packed states `values` are of unit length (to the 1e-9 of unit3_math.h); the first that is not is
+// named in err.  Nothing is normalised silently
+gsx_status check_direction_states(const HostProblem& P, const double* values, std::string& err);
 void compute_ordering(const HostProblem& P, int kind, std::vector<int>& order);
 // multilevel nested dissection of the vertices `verts` of the graph `adj` (nd.cpp); sets of at most `leaf` vertices and
 // the separators are ordered by `leaf_order` (appends to `out`)

@@ -437,6 +437,19 @@ static gsx_status gsx_update_impl(gsx_handle h, const gsx_problem_desc* desc, co
     h->err = "gsx_update: new_values does not hold exactly the states of the new variables";
     return GSX_E_INVALID;
   }
+  if (!P2.direction_vars.empty()) {  // the directions of the new Unit3 / EssentialMatrix states: unit, as gsx_set_values asks
+    int64_t src = 0;
+    for (int v = 0; v < P2.n_vars; ++v) {
+      if (old_of[v] >= 0) continue;
+      const int t = P2.types[v];
+      if (is_direction_type(t) && !direction_state_ok(t, new_values + src)) {
+        h->err = "gsx_update: new variable " + std::to_string(v) + " (key " + std::to_string((unsigned long long)P2.keys[v]) +
+                 "), a " + direction_type_name(t) + ": its direction is not of unit length";
+        return GSX_E_INVALID;
+      }
+      src += state_len(P2, v);
+    }
+  }
   // factors: kept by origin (same shape), and which variables the change touches
   std::vector<char> used(P1.n_factors, 0), affected(P2.n_vars, 0);
   int n_fadd = 0;

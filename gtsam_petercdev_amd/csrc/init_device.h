@@ -102,6 +102,8 @@ inline int64_t desc_state_size(const gsx_problem_desc* d, std::vector<int>* stat
       case GSX_VAR_POSE3: n += 12; break;
       case GSX_VAR_CAMERA: n += 17; break;
       case GSX_VAR_ROT3: n += 9; break;
+      case GSX_VAR_UNIT3: n += 3; break;
+      case GSX_VAR_ESSENTIAL: n += 12; break;
       default: n += d->var_dims[v];
     }
   }

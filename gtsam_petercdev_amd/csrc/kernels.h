@@ -186,7 +186,15 @@ enum { TL_SFM = 0, TL_BETWEEN_POSE2 = 1, TL_BETWEEN_POSE3 = 2, TL_GENERIC = 3, T
        // the absolute-measurement factors: every single-key form of GSX_F_GPS, GSX_F_POSE_TRANSLATION_PRIOR,
        // GSX_F_POSE_ROTATION_PRIOR, GSX_F_ATTITUDE and GSX_F_MAG in one list (sorted by ABS_* sub-kind), and the two
        // two-key forms that came with them: BetweenFactor<Rot3> and GPSFactorArmCalib
-       TL_ABSOLUTE = 22, TL_BETWEEN_ROT3 = 23, TL_GPS_CALIB = 24, kNumTypeLists = 25 };
+       TL_ABSOLUTE = 22, TL_BETWEEN_ROT3 = 23, TL_GPS_CALIB = 24,
+       // the epipolar factors, a list per form (each kernel knows its form at compile time, as the SENSOR forms do):
+       // EssentialMatrixFactor, EssentialMatrixFactor2, EssentialMatrixFactor3 (told from 2 by its 15 measurement doubles),
+       // EssentialMatrixFactor4<Cal3_S2>, EssentialMatrixConstraint
+       TL_ESSENTIAL = 25, TL_ESSENTIAL_DEPTH = 26, TL_ESSENTIAL_DEPTH_ROTATED = 27, TL_ESSENTIAL_CALIB = 28,
+       TL_ESSENTIAL_CONSTRAINT = 29,
+       // PriorFactor<Unit3> and PriorFactor<EssentialMatrix>: lists of their own, not TL_GENERIC, so that the generic
+       // kernels (local_coords) stay what they were for every graph without the two types
+       TL_PRIOR_UNIT3 = 30, TL_PRIOR_ESSENTIAL = 31, kNumTypeLists = 32 };
 // sub-kind of a TL_ABSOLUTE factor, in bits 16..23 of FactorRec::type_kind (its noise kind keeps bits 8..15)
 enum { ABS_GPS = 0, ABS_GPS_ARM = 1, ABS_TRANS_POSE2 = 2, ABS_TRANS_POSE3 = 3, ABS_ROT_POSE2 = 4, ABS_ROT_POSE3 = 5,
        ABS_ATT_ROT3 = 6, ABS_ATT_POSE3 = 7, ABS_MAG_ROT3 = 8, ABS_MAG_POSE3 = 9, ABS_MAG_POSE2 = 10 };
@@ -208,6 +216,7 @@ constexpr int kSensorListShift = TL_RANGE_POSE2_POINT_SENSOR - TL_RANGE_POSE2_PO
 inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
   switch (t) {
     case GSX_F_LINEAR: return -1;
+    case GSX_F_PRIOR: return vt0 == GSX_VAR_UNIT3 ? TL_PRIOR_UNIT3 : (vt0 == GSX_VAR_ESSENTIAL ? TL_PRIOR_ESSENTIAL : TL_GENERIC);
     case GSX_F_SFM: return TL_SFM;
     case GSX_F_SFM2: return TL_SFM2;
     case GSX_F_PROJECTION: return nmeas > 7 ? TL_PROJECTION_SENSOR : TL_PROJECTION;
@@ -229,6 +238,10 @@ inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
     case GSX_F_POSE_ROTATION_PRIOR:
     case GSX_F_ATTITUDE:
     case GSX_F_MAG: return TL_ABSOLUTE;
+    case GSX_F_ESSENTIAL: return TL_ESSENTIAL;
+    case GSX_F_ESSENTIAL_DEPTH: return nmeas > 6 ? TL_ESSENTIAL_DEPTH_ROTATED : TL_ESSENTIAL_DEPTH;
+    case GSX_F_ESSENTIAL_CALIB: return TL_ESSENTIAL_CALIB;
+    case GSX_F_ESSENTIAL_CONSTRAINT: return TL_ESSENTIAL_CONSTRAINT;
   }
   return TL_GENERIC;
 }

@@ -22,6 +22,7 @@
 #include "device_geometry.h"
 #include "gsx_internal.h"
 #include "kernels.h"
+#include "unit3_math.h"
 #include "wave_util.h"
 
 namespace gsx {
@@ -870,6 +871,269 @@ __global__ void __launch_bounds__(256) linearize_between_rot3_kernel(DevProblem 
   whiten_store<3, 7>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
 }
 
+// ---------------------------------------------------------------------------------------------
+// two-view geometry: the epipolar factors on a GSX_VAR_ESSENTIAL variable (state R 9, direction t 3; tangent omega 3, then
+// the direction's 2 in the basis B = t.basis(), unit3_math.h) and EssentialMatrixConstraint between two poses.  A list and
+// a kernel instance per form.  E = [t]x R is never formed: E v = t x (R v), E' v = R' (v x t).  Bases and the 5 x 5 chain
+// of EssentialMatrixFactor3 are applied a row at a time.  e and the rows of H stay in registers.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ V3 ld3(const double* p) { return V3{p[0], p[1], p[2]}; }
+// (row . b1, row . b2) of the basis B (3 x 2 row-major)
+__device__ __forceinline__ void row_times_basis(V3 row, const double* B, double* out) {
+  out[0] = row.x * B[0] + row.y * B[2] + row.z * B[4];
+  out[1] = row.x * B[1] + row.y * B[3] + row.z * B[5];
+}
+// EssentialMatrix::error (EssentialMatrix.cpp:104-114): e = vA' E vB; H (1 x 5) = [vA' E [-vB]x, vA' [-R vB]x B]
+//   vA' E [-vB]x = (vB x E' vA)',  vA' [-R vB]x = ((R vB) x vA)'
+template <bool WITH_H>
+__device__ __forceinline__ double epipolar_error(const M3& R, V3 t, V3 vA, V3 vB, double* H) {
+  const V3 RvB = mulv(R, vB);
+  if constexpr (WITH_H) {
+    const V3 EtvA = tmulv(R, cross(vA, t));
+    const V3 hr = cross(vB, EtvA);
+    double B[6];
+    const double tt[3] = {t.x, t.y, t.z};
+    unit3_basis(tt, B);
+    H[0] = hr.x; H[1] = hr.y; H[2] = hr.z;
+    row_times_basis(cross(RvB, vA), B, H + 3);
+  }
+  return dot(vA, cross(t, RvB));
+}
+// EssentialMatrixFactor (EssentialMatrixFactor.h:34-106): meas = vA, vB
+template <bool WITH_H>
+__device__ __forceinline__ void essential_eval(const double* x, const double* z, double (&e)[1], double* H) {
+  M3 R;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R.a[k] = x[k];
+  e[0] = epipolar_error<WITH_H>(R, ld3(x + 9), ld3(z), ld3(z + 3), H);
+}
+// EssentialMatrixFactor4<Cal3_S2> (:334-419): meas = pA, pB (pixels), K = (fx, fy, s, u0, v0) the second key.
+// Cal3_S2::calibrate with Dcal (Cal3_S2.cpp:53-69); HK = (E vB)[0:2]' DcalA + (E' vA)[0:2]' DcalB.  H = [HE (5), HK (5)]
+template <bool WITH_H>
+__device__ __forceinline__ void essential_calib_eval(const double* x, const double* K, const double* z, double (&e)[1], double* H) {
+  M3 R;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R.a[k] = x[k];
+  const V3 t = ld3(x + 9);
+  const double inv_fx = 1 / K[0], inv_fy = 1 / K[1], s = K[2];
+  const double inv_fx_s_inv_fy = inv_fx * s * inv_fy;
+  double c[4], dv[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const double du = z[2 * q] - K[3];
+    dv[q] = inv_fy * (z[2 * q + 1] - K[4]);
+    c[2 * q] = inv_fx * (du - s * dv[q]);
+    c[2 * q + 1] = dv[q];
+  }
+  const V3 vA{c[0], c[1], 1.0}, vB{c[2], c[3], 1.0};
+  e[0] = epipolar_error<WITH_H>(R, t, vA, vB, H);
+  if constexpr (WITH_H) {
+    const V3 EvB = cross(t, mulv(R, vB)), EtvA = tmulv(R, cross(vA, t));
+    const double g[4] = {EvB.x, EvB.y, EtvA.x, EtvA.y};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) H[5 + k] = 0.0;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {  // Dcal of point q: rows (-inv_fx x, inv_fx s inv_fy dv, -inv_fx y, -inv_fx, inv_fx s inv_fy), (0, -inv_fy y, 0, 0, -inv_fy)
+      const double g0 = g[2 * q], g1 = g[2 * q + 1], px = c[2 * q], py = c[2 * q + 1];
+      H[5] += g0 * (-inv_fx * px);
+      H[6] += g0 * (inv_fx_s_inv_fy * dv[q]) + g1 * (-inv_fy * py);
+      H[7] += g0 * (-inv_fx * py);
+      H[8] += g0 * (-inv_fx);
+      H[9] += g0 * inv_fx_s_inv_fy + g1 * (-inv_fy);
+    }
+  }
+}
+// EssentialMatrixFactor2 (:112-229): meas = dP1, pn, f; the inverse depth d the second key.  dP2 = R' (dP1 - d t),
+// e = f (Project(dP2) - pn); DE = f Dpn [[dP2]x, -d R' B], Dd = -f Dpn R' t.  ROTATED: EssentialMatrixFactor3 (:237-317),
+// cRb (9) behind the measurement: (R, t) <- (cRb R cRb', normalize(cRb t)) (EssentialMatrix::rotate, EssentialMatrix.cpp:
+// 73-101) and each row of DE times [cRb 0; 0 Bq' cRb B] (Rot3::rotate(Unit3), Rot3.cpp:110-117), Bq the basis of the
+// ROTATED direction.  H row-major 2 x 6: DE (5), Dd (1)
+template <bool ROTATED, bool WITH_H>
+__device__ __forceinline__ void essential_depth_eval(const double* x, double d, const double* z, double (&e)[2], double* H) {
+  M3 R;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R.a[k] = x[k];
+  V3 t = ld3(x + 9);
+  M3 C;
+  if constexpr (ROTATED) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) C.a[k] = z[6 + k];
+    R = mul(mul(C, R), transpose(C));
+    const V3 q = mulv(C, t);
+    t = (1.0 / sqrt(dot(q, q))) * q;
+  }
+  const double f = z[5];
+  const V3 w = ld3(z) - d * t;
+  const V3 p2 = tmulv(R, w);
+  const double iz = 1.0 / p2.z, u = p2.x * iz, v = p2.y * iz;
+  e[0] = f * (u - z[3]);
+  e[1] = f * (v - z[4]);
+  if constexpr (WITH_H) {
+    double Bq[6];
+    const double tt[3] = {t.x, t.y, t.z};
+    unit3_basis(tt, Bq);
+    const V3 Rt_t = tmulv(R, t);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      // row r of f Dpn: f / z (1 0 -u | 0 1 -v)
+      const V3 g = r == 0 ? V3{f * iz, 0.0, -f * iz * u} : V3{0.0, f * iz, -f * iz * v};
+      double* h = H + 6 * r;
+      const V3 hw = cross(g, p2);          // g' [dP2]x = (g x dP2)'
+      h[0] = hw.x; h[1] = hw.y; h[2] = hw.z;
+      const V3 Rg = mulv(R, g);            // g' R' = (R g)'
+      row_times_basis((-d) * Rg, Bq, h + 3);
+      h[5] = -dot(g, Rt_t);
+      if constexpr (ROTATED) {
+        const V3 hb = tmulv(C, V3{h[0], h[1], h[2]});  // (h_w' cRb)'
+        const V3 gq{h[3] * Bq[0] + h[4] * Bq[1], h[3] * Bq[2] + h[4] * Bq[3], h[3] * Bq[4] + h[4] * Bq[5]};
+        double B[6];
+        unit3_basis(x + 9, B);
+        h[0] = hb.x; h[1] = hb.y; h[2] = hb.z;
+        row_times_basis(tmulv(C, gq), B, h + 3);
+      }
+    }
+  }
+}
+// EssentialMatrixConstraint (EssentialMatrixConstraint.cpp:45-77): h = p1^-1 p2, hx = FromPose3(h) = (R_h, normalize(t_h)),
+// e = measured.localCoordinates(hx) = (Logmap(Rz' R_h), tz.localCoordinates(dir)).  D_hx = [I 0; 0 G], G = Bd' Dn R_h with
+// Dn = (|t|^2 I - t t') / |t|^3 (Point3.cpp normalize) and Bd the basis of dir; Hp2 = D_hx, Hp1 = -D_hx Ad(h^-1).  A zero
+// t_h divides by zero as the reference does: the non-finite values go on as they are.  H1, H2 row-major 5 x 6
+template <bool WITH_H>
+__device__ __forceinline__ void essential_constraint_eval(const double* x1, const double* x2, const double* z, double (&e)[5],
+                                                          double* H1, double* H2) {
+  const P3 h = between(load_pose3(x1), load_pose3(x2));
+  const double n2 = dot(h.t, h.t), nrm = sqrt(n2);
+  const V3 dir = (1.0 / nrm) * h.t;
+  M3 Z;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Z.a[k] = z[k];
+  const V3 w = so3_logmap(mul(transpose(Z), h.R));
+  e[0] = w.x; e[1] = w.y; e[2] = w.z;
+  const double dd[3] = {dir.x, dir.y, dir.z};
+  unit3_local(z + 9, dd, e + 3);
+  if constexpr (WITH_H) {
+    double Bd[6], G[6], Ad[36];
+    unit3_basis(dd, Bd);
+    const double s = 1.0 / (n2 * nrm);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const V3 b{Bd[r], Bd[2 + r], Bd[4 + r]};
+      const V3 bn = s * (n2 * b - dot(b, h.t) * h.t);  // (b' Dn)'
+      const V3 g = tmulv(h.R, bn);                      // (b' Dn R_h)'
+      G[3 * r] = g.x; G[3 * r + 1] = g.y; G[3 * r + 2] = g.z;
+    }
+    pose3_adjoint(inverse(h), Ad);
+#pragma unroll
+    for (int i = 0; i < 30; ++i) H2[i] = 0.0;
+    H2[0] = H2[7] = H2[14] = 1.0;
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) H2[6 * (3 + r) + 3 + c] = G[3 * r + c];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) H1[6 * r + c] = -Ad[6 * r + c];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+        H1[6 * (3 + r) + c] = -(G[3 * r] * Ad[18 + c] + G[3 * r + 1] * Ad[24 + c] + G[3 * r + 2] * Ad[30 + c]);
+    }
+  }
+}
+// the five forms, told at compile time by their list: M rows, the tangent dimensions D0 + D1 of the two keys (D1 = 0: one)
+template <int TL>
+struct EssentialShape;
+template <> struct EssentialShape<TL_ESSENTIAL> { static constexpr int M = 1, D0 = 5, D1 = 0; };
+template <> struct EssentialShape<TL_ESSENTIAL_DEPTH> { static constexpr int M = 2, D0 = 5, D1 = 1; };
+template <> struct EssentialShape<TL_ESSENTIAL_DEPTH_ROTATED> { static constexpr int M = 2, D0 = 5, D1 = 1; };
+template <> struct EssentialShape<TL_ESSENTIAL_CALIB> { static constexpr int M = 1, D0 = 5, D1 = 5; };
+template <> struct EssentialShape<TL_ESSENTIAL_CONSTRAINT> { static constexpr int M = 5, D0 = 6, D1 = 6; };
+template <> struct EssentialShape<TL_PRIOR_UNIT3> { static constexpr int M = 2, D0 = 2, D1 = 0; };
+template <> struct EssentialShape<TL_PRIOR_ESSENTIAL> { static constexpr int M = 5, D0 = 5, D1 = 0; };
+// e (M) and, WITH_H, H (M x (D0 + D1) row-major: the first key's columns, then the second's)
+template <int TL, bool WITH_H>
+__device__ __forceinline__ void essential_family_eval(const FactorRec& fr, const DevProblem& P, const double* values,
+                                                      double (&e)[EssentialShape<TL>::M], double* H) {
+  const double* x = values + fr.s0;
+  const double* z = P.meas + fr.meas_off;
+  if constexpr (TL == TL_PRIOR_UNIT3 || TL == TL_PRIOR_ESSENTIAL) {
+    // PriorFactor (gtsam/nonlinear/PriorFactor.h:98-102): e = -Local(x, prior), H = I; the charts of unit3_math.h, an
+    // EssentialMatrix's (Logmap(Rx' Rz), tx.localCoordinates(tz)) (EssentialMatrix.h:97-103)
+    constexpr int M = EssentialShape<TL>::M;
+    double l[M];
+    if constexpr (TL == TL_PRIOR_UNIT3) {
+      unit3_local(x, z, l);
+    } else {
+      M3 X, Z;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        X.a[k] = x[k];
+        Z.a[k] = z[k];
+      }
+      const V3 w = so3_logmap(mul(transpose(X), Z));
+      l[0] = w.x; l[1] = w.y; l[2] = w.z;
+      unit3_local(x + 9, z + 9, l + 3);
+    }
+#pragma unroll
+    for (int r = 0; r < M; ++r) e[r] = -l[r];
+    if constexpr (WITH_H) {
+#pragma unroll
+      for (int r = 0; r < M; ++r)
+#pragma unroll
+        for (int c = 0; c < M; ++c) H[r * M + c] = (r == c) ? 1.0 : 0.0;
+    }
+  } else if constexpr (TL == TL_ESSENTIAL) {
+    essential_eval<WITH_H>(x, z, e, H);
+  } else if constexpr (TL == TL_ESSENTIAL_CALIB) {
+    essential_calib_eval<WITH_H>(x, values + fr.s1, z, e, H);
+  } else if constexpr (TL == TL_ESSENTIAL_CONSTRAINT) {
+    double H1[WITH_H ? 30 : 1], H2[WITH_H ? 30 : 1];
+    essential_constraint_eval<WITH_H>(x, values + fr.s1, z, e, H1, H2);
+    if constexpr (WITH_H) {
+#pragma unroll
+      for (int r = 0; r < 5; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          H[12 * r + c] = H1[6 * r + c];
+          H[12 * r + 6 + c] = H2[6 * r + c];
+        }
+    }
+  } else {
+    essential_depth_eval<TL == TL_ESSENTIAL_DEPTH_ROTATED, WITH_H>(x, values[fr.s1], z, e, H);
+  }
+}
+template <int TL>
+__global__ void __launch_bounds__(256) linearize_essential_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                  double* jac) {
+  constexpr int M = EssentialShape<TL>::M, D = EssentialShape<TL>::D0 + EssentialShape<TL>::D1;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FactorRec fr = P.frec[list[i]];
+  double e[M], H[M * D], J[M * (D + 1)];
+  essential_family_eval<TL, true>(fr, P, values, e, H);
+#pragma unroll
+  for (int c = 0; c < D; ++c)
+#pragma unroll
+    for (int r = 0; r < M; ++r) J[c * M + r] = H[r * D + c];
+#pragma unroll
+  for (int r = 0; r < M; ++r) J[D * M + r] = -e[r];
+  whiten_store<M, D + 1>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+template <int TL>
+__global__ void __launch_bounds__(256) error_essential_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                              double* partials) {
+  constexpr int M = EssentialShape<TL>::M;
+  double acc = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const FactorRec fr = P.frec[list[i]];
+    double e[M];
+    essential_family_eval<TL, false>(fr, P, values, e, nullptr);
+    acc += whitened_half_sqnorm<M>(e, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off);
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
 void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
                       const double* values, double* jac, DevStatus* status, hipStream_t st, const SmartDev* smart) {
   auto grid = [](int n) { return dim3((n + 255) / 256); };
@@ -925,6 +1189,13 @@ void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeL
   run(linearize_absolute_kernel, TL_ABSOLUTE);
   run(linearize_between_rot3_kernel, TL_BETWEEN_ROT3);
   run(linearize_gps_calib_kernel, TL_GPS_CALIB);
+  run(linearize_essential_kernel<TL_ESSENTIAL>, TL_ESSENTIAL);
+  run(linearize_essential_kernel<TL_ESSENTIAL_DEPTH>, TL_ESSENTIAL_DEPTH);
+  run(linearize_essential_kernel<TL_ESSENTIAL_DEPTH_ROTATED>, TL_ESSENTIAL_DEPTH_ROTATED);
+  run(linearize_essential_kernel<TL_ESSENTIAL_CALIB>, TL_ESSENTIAL_CALIB);
+  run(linearize_essential_kernel<TL_ESSENTIAL_CONSTRAINT>, TL_ESSENTIAL_CONSTRAINT);
+  run(linearize_essential_kernel<TL_PRIOR_UNIT3>, TL_PRIOR_UNIT3);
+  run(linearize_essential_kernel<TL_PRIOR_ESSENTIAL>, TL_PRIOR_ESSENTIAL);
   if (type_counts[TL_SMART] && smart) {   // triangulate (cache consulted and updated), then marginalize the landmark
     launch_smart_triangulate(P, type_lists[TL_SMART], type_counts[TL_SMART], values, *smart, st);
     launch_smart_linearize(P, type_lists[TL_SMART], type_counts[TL_SMART], *smart, jac, st);
@@ -1160,8 +1431,13 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
   // (likewise a graph without smart factors keeps the shares it had before TL_SMART came, and one without the translation
   // factors those it had before TL_TRANSLATION and TL_BATA came)
   // (and one without the absolute-measurement lists those it had before they came)
-  const int held = type_counts[TL_ABSOLUTE] + type_counts[TL_BETWEEN_ROT3] + type_counts[TL_GPS_CALIB] > 0
+  // (and one without the epipolar lists those it had before they came)
+  int n_essential = 0;
+  for (int k = TL_ESSENTIAL; k < kNumTypeLists; ++k) n_essential += type_counts[k];
+  const int held = n_essential > 0
                        ? kNumTypeLists
+                   : type_counts[TL_ABSOLUTE] + type_counts[TL_BETWEEN_ROT3] + type_counts[TL_GPS_CALIB] > 0
+                       ? TL_ESSENTIAL
                    : type_counts[TL_TRANSLATION] + type_counts[TL_BATA] > 0
                        ? TL_ABSOLUTE
                        : (type_counts[TL_SMART] > 0 ? TL_TRANSLATION : (new_lists ? TL_SMART : TL_PROJECTION_SENSOR));
@@ -1197,6 +1473,13 @@ void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists
       case TL_ABSOLUTE: error_absolute_kernel<<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_BETWEEN_ROT3: error_list_kernel<GSX_F_BETWEEN, GSX_VAR_ROT3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_GPS_CALIB: error_list_kernel<GSX_F_GPS, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_ESSENTIAL: error_essential_kernel<TL_ESSENTIAL><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_ESSENTIAL_DEPTH: error_essential_kernel<TL_ESSENTIAL_DEPTH><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_ESSENTIAL_DEPTH_ROTATED: error_essential_kernel<TL_ESSENTIAL_DEPTH_ROTATED><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_ESSENTIAL_CALIB: error_essential_kernel<TL_ESSENTIAL_CALIB><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_ESSENTIAL_CONSTRAINT: error_essential_kernel<TL_ESSENTIAL_CONSTRAINT><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_PRIOR_UNIT3: error_essential_kernel<TL_PRIOR_UNIT3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
+      case TL_PRIOR_ESSENTIAL: error_essential_kernel<TL_PRIOR_ESSENTIAL><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
       case TL_SMART:   // triangulate at `values` (cache consulted and updated), then the reprojection errors
         launch_smart_triangulate(P, type_lists[k], n, values, *smart, st);
         launch_smart_error(P, type_lists[k], n, *smart, out, nb, st);
@@ -1424,7 +1707,9 @@ __global__ void __launch_bounds__(256) retract_kernel(DevProblem P, const double
   } else if (type == GSX_VAR_POSE2) {
     const P2 r = compose(load_pose2(x), load_pose2(d));
     y[0] = r.x; y[1] = r.y; y[2] = theta(r);
-  } else if (type == GSX_VAR_ROT3) {  // R Expmap(omega): the rotation part of Pose3::Expmap (SO3.cpp:61-112)
+  } else if (type == GSX_VAR_ROT3 || type == GSX_VAR_ESSENTIAL) {
+    // R Expmap(omega): the rotation part of Pose3::Expmap (SO3.cpp:61-112); an EssentialMatrix retracts its direction
+    // behind it (EssentialMatrix.h:92-94)
     const double xi[6] = {d[0], d[1], d[2], 0.0, 0.0, 0.0};
     M3 X;
 #pragma unroll
@@ -1432,6 +1717,17 @@ __global__ void __launch_bounds__(256) retract_kernel(DevProblem P, const double
     const M3 Y = mul(X, pose3_expmap(xi).R);
 #pragma unroll
     for (int i = 0; i < 9; ++i) y[i] = Y.a[i];
+    if (type == GSX_VAR_ESSENTIAL) {
+      const double p[3] = {x[9], x[10], x[11]}, v[2] = {d[3], d[4]};
+      double q[3];
+      unit3_retract(p, v, q);
+      y[9] = q[0]; y[10] = q[1]; y[11] = q[2];
+    }
+  } else if (type == GSX_VAR_UNIT3) {  // Unit3::retract (unit3_math.h)
+    const double p[3] = {x[0], x[1], x[2]}, v[2] = {d[0], d[1]};
+    double q[3];
+    unit3_retract(p, v, q);
+    y[0] = q[0]; y[1] = q[1]; y[2] = q[2];
   } else {
     double xi[6];
 #pragma unroll
@@ -2207,7 +2503,7 @@ void launch_mask_copy(const double* in, const unsigned char* mask, int64_t n, do
 }
 
 __device__ inline int state_len(int type, int dim) {
-  return type == GSX_VAR_POSE2 ? 3 : (type == GSX_VAR_POSE3 ? 12 : (type == GSX_VAR_CAMERA ? 17 : (type == GSX_VAR_ROT3 ? 9 : dim)));
+  return type == GSX_VAR_POSE2 ? 3 : (type == GSX_VAR_POSE3 ? 12 : (type == GSX_VAR_CAMERA ? 17 : (type == GSX_VAR_ROT3 ? 9 : (type == GSX_VAR_UNIT3 ? 3 : (type == GSX_VAR_ESSENTIAL ? 12 : dim)))));
 }
 __global__ void scatter_states_kernel(DevProblem P, const int* vars, const int* src_off, int n, const double* src,
                                       double* values) {

@@ -13,26 +13,20 @@ static int state_dim(int type, int dim) {
     case GSX_VAR_POSE3: return 12;
     case GSX_VAR_CAMERA: return 17;
     case GSX_VAR_ROT3: return 9;
+    case GSX_VAR_UNIT3: return 3;
+    case GSX_VAR_ESSENTIAL: return 12;
   }
   return -1;
 }
 
-// Unit3::basis (gtsam/geometry/Unit3.cpp:72-81, 128-138): b1 = normalize(n x axis) with the axis of the smallest |n_i| (ties
-// go to the earlier axis, as the chain of <= there), b2 = n x b1.  B row-major 3 x 2.
-void unit3_basis(const double* n, double* B) {
-  const double mx = std::fabs(n[0]), my = std::fabs(n[1]), mz = std::fabs(n[2]);
-  double a[3] = {0, 0, 0};
-  if (mx <= my && mx <= mz) a[0] = 1;
-  else if (my <= mx && my <= mz) a[1] = 1;
-  else a[2] = 1;
-  double b1[3] = {n[1] * a[2] - n[2] * a[1], n[2] * a[0] - n[0] * a[2], n[0] * a[1] - n[1] * a[0]};
-  const double nrm = std::sqrt(b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2]);
-  for (double& x : b1) x /= nrm;
-  const double b2[3] = {n[1] * b1[2] - n[2] * b1[1], n[2] * b1[0] - n[0] * b1[2], n[0] * b1[1] - n[1] * b1[0]};
-  for (int r = 0; r < 3; ++r) {
-    B[2 * r] = b1[r];
-    B[2 * r + 1] = b2[r];
-  }
+gsx_status check_direction_states(const HostProblem& P, const double* values, std::string& err) {
+  for (int v : P.direction_vars)
+    if (!direction_state_ok(P.types[v], values + P.state_off[v])) {
+      err = "variable " + std::to_string(v) + " (key " + std::to_string((unsigned long long)P.keys[v]) + "), a " +
+            direction_type_name(P.types[v]) + ": its direction is not of unit length";
+      return GSX_E_INVALID;
+    }
+  return GSX_OK;
 }
 
 gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string& err) {
@@ -45,6 +39,7 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
   P.con_factor.clear();
   P.con_row.clear();
   P.con_mu.clear();
+  P.direction_vars.clear();
   P.keys.assign(d->var_keys, d->var_keys + d->n_vars);
   P.types.assign(d->var_types, d->var_types + d->n_vars);
   P.dims.assign(d->var_dims, d->var_dims + d->n_vars);
@@ -57,13 +52,14 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
       return GSX_E_INVALID;
     }
     const int t = P.types[v];
-    const int expect[5] = {P.dims[v], 3, 6, 9, 3};
-    if (t < 0 || t > 4 || P.dims[v] != expect[t] || P.dims[v] <= 0 || (t == GSX_VAR_VECTOR && P.dims[v] > 64)) {
+    const int expect[7] = {P.dims[v], 3, 6, 9, 3, 2, 5};
+    if (t < 0 || t > 6 || P.dims[v] != expect[t] || P.dims[v] <= 0 || (t == GSX_VAR_VECTOR && P.dims[v] > 64)) {
       err = "bad variable type/dim at variable " + std::to_string(v);
       return GSX_E_INVALID;
     }
     P.state_off[v] = (int)P.state_size;
     P.tan_off[v] = (int)P.tan_size;
+    if (is_direction_type(t)) P.direction_vars.push_back(v);
     P.state_size += state_dim(t, P.dims[v]);
     P.tan_size += P.dims[v];
   }
@@ -111,8 +107,19 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
         break;
       case GSX_F_PRIOR:
         ok = ok && nk == 1 && m == dv(0) && nmeas == state_dim(tv(0), dv(0)) && m <= 9;
+        if (ok && is_direction_type(tv(0)) && !direction_state_ok(tv(0), P.meas.data() + P.f_meas_ptr[f])) {
+          err = "factor " + std::to_string(f) + ": the direction of the prior on a " + direction_type_name(tv(0)) +
+                " is not of unit length";
+          return GSX_E_INVALID;
+        }
         break;
       case GSX_F_BETWEEN:
+        for (int k = 0; k < nk && k < 2; ++k)  // neither type is a group
+          if (is_direction_type(tv(k))) {
+            err = "factor " + std::to_string(f) + ": GSX_F_BETWEEN on variable " + std::to_string(P.f_vars[P.f_key_ptr[f] + k]) +
+                  ", a " + direction_type_name(tv(k)) + " (not a group)";
+            return GSX_E_INVALID;
+          }
         ok = ok && nk == 2 && tv(0) == tv(1) && dv(0) == dv(1) && tv(0) != GSX_VAR_CAMERA && m == dv(0) &&
              nmeas == state_dim(tv(0), dv(0)) && m <= 9;
         break;
@@ -195,6 +202,23 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
         ok = ok && nk == 1 &&
              (((tv(0) == GSX_VAR_ROT3 || tv(0) == GSX_VAR_POSE3) && m == 3) || (tv(0) == GSX_VAR_POSE2 && m == 2)) &&
              nmeas == 3 * m;
+        break;
+      case GSX_F_ESSENTIAL:  // vA, vB
+        ok = ok && nk == 1 && tv(0) == GSX_VAR_ESSENTIAL && m == 1 && nmeas == 6;
+        break;
+      case GSX_F_ESSENTIAL_DEPTH:  // dP1, pn, f; with cRb behind them EssentialMatrixFactor3
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_ESSENTIAL && tv(1) == GSX_VAR_VECTOR && dv(1) == 1 && m == 2 &&
+             (nmeas == 6 || nmeas == 15);
+        break;
+      case GSX_F_ESSENTIAL_CALIB:  // pA, pB
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_ESSENTIAL && tv(1) == GSX_VAR_VECTOR && dv(1) == 5 && m == 1 && nmeas == 4;
+        break;
+      case GSX_F_ESSENTIAL_CONSTRAINT:  // the measured E: R, direction
+        ok = ok && nk == 2 && tv(0) == GSX_VAR_POSE3 && tv(1) == GSX_VAR_POSE3 && m == 5 && nmeas == 12;
+        if (ok && !direction_state_ok(GSX_VAR_ESSENTIAL, P.meas.data() + P.f_meas_ptr[f])) {
+          err = "factor " + std::to_string(f) + ": the direction of the measured E of GSX_F_ESSENTIAL_CONSTRAINT is not of unit length";
+          return GSX_E_INVALID;
+        }
         break;
       default:
         ok = false;

@@ -1003,8 +1003,9 @@ int64_t gsx_state_size(gsx_handle h) { return h ? h->P.state_size : 0; }
 int64_t gsx_tangent_size(gsx_handle h) { return h ? h->P.tan_size : 0; }
 int64_t gsx_jacobian_size(gsx_handle h) { return h ? h->P.jac_size : 0; }
 
-gsx_status gsx_set_values(gsx_handle h, const double* packed, int64_t n) {
-  if (!h || n != h->P.state_size || (!packed && n > 0)) return GSX_E_INVALID;
+// the copy of gsx_set_values without its check of the directions: for the zeros a handle of GSX_F_LINEAR factors is given
+// (gsx_solve_gfg, gsx_solve_gfg_h), which reads no state
+static gsx_status set_values_unchecked(gsx_handle h, const double* packed, int64_t n) {
   gsx_status st = need_device(h);
   if (st != GSX_OK) return st;
   hipSetDevice(h->device);
@@ -1014,6 +1015,12 @@ gsx_status gsx_set_values(gsx_handle h, const double* packed, int64_t n) {
   }
   h->values_written();
   return GSX_OK;
+}
+
+gsx_status gsx_set_values(gsx_handle h, const double* packed, int64_t n) {
+  if (!h || n != h->P.state_size || (!packed && n > 0)) return GSX_E_INVALID;
+  if (!h->P.direction_vars.empty() && check_direction_states(h->P, packed, h->err) != GSX_OK) return GSX_E_INVALID;
+  return set_values_unchecked(h, packed, n);
 }
 
 gsx_status gsx_get_values(gsx_handle h, double* packed, int64_t n) {
@@ -1597,7 +1604,7 @@ gsx_status gsx_solve_gfg_h(gsx_handle h, const double* blocks, int64_t n_blocks,
   if (st != GSX_OK) return st;
   if (!h->values_set) {
     std::vector<double> zeros(h->P.state_size, 0.0);
-    st = gsx_set_values(h, zeros.data(), h->P.state_size);
+    st = set_values_unchecked(h, zeros.data(), h->P.state_size);
     if (st != GSX_OK) return st;
   }
   h->linear_graph_given();
@@ -1662,7 +1669,7 @@ gsx_status gsx_solve_gfg(const gsx_problem_desc* desc, const uint64_t* ordering,
   else st = gsx_compute_ordering(h, GSX_ORDER_MINDEGREE, ord.data());
   if (st == GSX_OK) st = gsx_set_ordering(h, ord.data(), desc->n_vars);
   std::vector<double> zeros(h->P.state_size, 0.0);
-  if (st == GSX_OK) st = gsx_set_values(h, zeros.data(), h->P.state_size);
+  if (st == GSX_OK) st = set_values_unchecked(h, zeros.data(), h->P.state_size);
   if (st == GSX_OK) st = gsx_linearize(h);
   if (st == GSX_OK) st = gsx_solve(h, 0.0, 0, 0, 0, delta_out, n, bad_key);
   gsx_destroy(h);

@@ -278,6 +278,10 @@ def _unwrap(type_code, s):
         return PinholeCameraCal3Bundler.from_state(s)
     if type_code == A.VAR_ROT3:
         return Rot3.from_state(s)
+    if type_code == A.VAR_UNIT3:
+        return Unit3.from_state(s)
+    if type_code == A.VAR_ESSENTIAL:
+        return EssentialMatrix.from_state(s)
     return np.array(s)
 
 
@@ -430,13 +434,15 @@ def BetweenFactor(key1, key2, measured, model=None):
     v = _wrap_value(measured)
     if v.type_code == A.VAR_CAMERA:
         raise ValueError("BetweenFactor<camera> is not on the supported path")
+    if v.type_code in (A.VAR_UNIT3, A.VAR_ESSENTIAL):
+        raise ValueError("BetweenFactor on a Unit3 or an EssentialMatrix: neither is a group")
     f = _Factor(A.F_BETWEEN, [key1, key2], v.dim, v.state(), model)
     f.value_type = v.type_code
     return f
 
 
 BetweenFactorPose2 = BetweenFactorPose3 = BetweenFactorRot3 = BetweenFactorPoint2 = BetweenFactorPoint3 = BetweenFactor
-PriorFactorPose2 = PriorFactorPose3 = PriorFactorRot3 = PriorFactorPoint2 = PriorFactorPoint3 = PriorFactor
+PriorFactorPose2 = PriorFactorPose3 = PriorFactorRot3 = PriorFactorUnit3 = PriorFactorEssentialMatrix = PriorFactorPoint2 = PriorFactorPoint3 = PriorFactor
 
 
 def GeneralSFMFactor(measured, model, cameraKey, landmarkKey):
@@ -542,8 +548,12 @@ GeneralSFMFactor2Cal3_S2 = GeneralSFMFactor2
 
 
 class Unit3:
-    """gtsam/geometry/Unit3.h, minimal: the constructor normalises (Unit3.h:70-79) and leaves (0, 0, 0) alone — it is what
-    TranslationRecovery compares zero-translation edges against (TranslationRecovery.cpp:55)."""
+    """gtsam/geometry/Unit3.h: a point on the unit sphere.  The constructor normalises (Unit3.h:70-79) and leaves (0, 0, 0)
+    alone — it is what TranslationRecovery compares zero-translation edges against (TranslationRecovery.cpp:55).  As a
+    VALUE it is the variable GSX_VAR_UNIT3: state the unit vector, tangent 2 in basis()."""
+
+    type_code = A.VAR_UNIT3
+    dim = 2
 
     def __init__(self, *args):
         if len(args) == 0:
@@ -560,6 +570,44 @@ class Unit3:
 
     unitVector = point3
 
+    def state(self):
+        return self.p
+
+    @staticmethod
+    def from_state(s):
+        u = Unit3()
+        u.p = np.array(s[:3], dtype=float)   # as stored: nothing is normalised again
+        return u
+
+    def basis(self):
+        """Unit3::basis (Unit3.cpp:72-81, 128-138): 3 x 2."""
+        n = self.p
+        m = np.abs(n)
+        axis = np.zeros(3)
+        axis[0 if (m[0] <= m[1] and m[0] <= m[2]) else (1 if (m[1] <= m[0] and m[1] <= m[2]) else 2)] = 1.0
+        b1 = np.cross(n, axis)
+        b1 = b1 / math.sqrt(b1 @ b1)
+        return np.stack([b1, np.cross(n, b1)], axis=1)
+
+    def retract(self, v):
+        """Unit3::retract (Unit3.cpp:255-282)."""
+        xi = self.basis() @ np.asarray(v, dtype=float).reshape(2)
+        theta = math.sqrt(xi @ xi)
+        st = 1.0 if theta < np.finfo(float).eps else math.sin(theta) / theta
+        return Unit3(math.cos(theta) * self.p + st * xi)
+
+    def localCoordinates(self, other: "Unit3"):
+        """Unit3::localCoordinates (Unit3.cpp:285-303)."""
+        x = float(self.p @ other.p)
+        z = 1.0 - x * x
+        if z < np.finfo(float).eps:
+            if x <= 0:
+                return np.array([math.pi, 0.0])
+            y = 1.0 - (x - 1.0) / 3.0
+        else:
+            y = math.acos(x) / math.sqrt(z)
+        return self.basis().T @ (y * (other.p - x * self.p))
+
     def dot(self, q: "Unit3") -> float:
         return float(self.p[0] * q.p[0] + self.p[1] * q.p[1] + self.p[2] * q.p[2])
 
@@ -568,6 +616,94 @@ class Unit3:
 
     def __repr__(self):
         return f"Unit3({self.p[0]:.6g}, {self.p[1]:.6g}, {self.p[2]:.6g})"
+
+
+def _so3_logmap(R):
+    """SO3::Logmap (gtsam/geometry/SO3.cpp:299-375)."""
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr + 1.0 < 1e-3:
+        k = 2 if (R[2, 2] > R[1, 1] and R[2, 2] > R[0, 0]) else (1 if R[1, 1] > R[0, 0] else 0)
+        i, j = (k + 1) % 3, (k + 2) % 3
+        W = R[j, i] - R[i, j]
+        Q1, Q2, Q3 = 2.0 + 2.0 * R[k, k], R[k, i] + R[i, k], R[j, k] + R[k, j]
+        norm = math.sqrt(Q1 * Q1 + Q2 * Q2 + Q3 * Q3 + W * W)
+        sgn = -1.0 if W < 0 else 1.0
+        scale = sgn * 0.5 / math.sqrt(Q1) * (math.pi - (2 * sgn * W) / norm)
+        w = np.zeros(3)
+        w[k], w[i], w[j] = scale * Q1, scale * Q2, scale * Q3
+        return w
+    tr_3 = tr - 3.0
+    if tr_3 < -1e-6:
+        theta = math.acos((tr - 1.0) / 2.0)
+        mag = theta / (2.0 * math.sin(theta))
+    else:
+        mag = 0.5 - tr_3 / 12.0 + tr_3 * tr_3 / 60.0
+    return mag * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+
+
+class EssentialMatrix:
+    """gtsam/geometry/EssentialMatrix.h: a rotation aRb and a direction aTb; E = [t]x R.  As a VALUE it is the variable
+    GSX_VAR_ESSENTIAL: state R row-major (9), then the direction (3); tangent omega (3), then the direction's 2."""
+
+    type_code = A.VAR_ESSENTIAL
+    dim = 5
+
+    def __init__(self, aRb: Optional[Rot3] = None, aTb: Optional[Unit3] = None):
+        self.R_ = aRb if aRb is not None else Rot3()
+        self.t_ = aTb if aTb is not None else Unit3(1.0, 0.0, 0.0)
+
+    @staticmethod
+    def FromPose3(aPb: "Pose3"):
+        """EssentialMatrix::FromPose3 (EssentialMatrix.cpp:27-45)."""
+        return EssentialMatrix(aPb.rotation(), Unit3(aPb.translation()))
+
+    @staticmethod
+    def FromRotationAndDirection(aRb, aTb):
+        return EssentialMatrix(aRb, aTb)
+
+    @staticmethod
+    def Homogeneous(p):
+        p = np.asarray(p, dtype=float).reshape(2)
+        return np.array([p[0], p[1], 1.0])
+
+    @staticmethod
+    def from_state(s):
+        return EssentialMatrix(Rot3.from_state(s[:9]), Unit3.from_state(s[9:12]))
+
+    def state(self):
+        return np.concatenate([self.R_.R.reshape(9), self.t_.p])
+
+    def rotation(self):
+        return self.R_
+
+    def direction(self):
+        return self.t_
+
+    def matrix(self):
+        return _skew(self.t_.p) @ self.R_.R
+
+    def retract(self, xi):
+        """EssentialMatrix.h:92-94: (R Expmap(xi[:3]), t.retract(xi[3:]))."""
+        xi = np.asarray(xi, dtype=float).reshape(5)
+        return EssentialMatrix(self.R_.compose(Rot3.Expmap(xi[:3])), self.t_.retract(xi[3:]))
+
+    def localCoordinates(self, other: "EssentialMatrix"):
+        """EssentialMatrix.h:97-103."""
+        return np.concatenate([_so3_logmap(self.R_.R.T @ other.R_.R), self.t_.localCoordinates(other.t_)])
+
+    def rotate(self, cRb: Rot3):
+        """EssentialMatrix::rotate (EssentialMatrix.cpp:73-101): E in the camera frame."""
+        return EssentialMatrix(Rot3(cRb.R @ self.R_.R @ cRb.R.T), Unit3(cRb.R @ self.t_.p))
+
+    def error(self, vA, vB):
+        """EssentialMatrix::error (EssentialMatrix.cpp:104-114): vA' E vB."""
+        return float(np.asarray(vA, dtype=float) @ self.matrix() @ np.asarray(vB, dtype=float))
+
+    def equals(self, o, tol=1e-8):
+        return self.R_.equals(o.R_, tol) and self.t_.equals(o.t_, tol)
+
+    def __repr__(self):
+        return f"EssentialMatrix(R={self.R_.R.tolist()}, t={self.t_})"
 
 
 def _direction(w_aZb) -> np.ndarray:
@@ -675,6 +811,57 @@ def MagPoseFactorPose3(pose_key, measured, scale, direction, bias, model, body_P
     return _mag_pose(pose_key, measured, scale, direction, bias, model, body_P_sensor, 3)
 
 
+# ---- two-view geometry (gtsam/slam/EssentialMatrixFactor.h, EssentialMatrixConstraint.h): the reference's argument orders -
+def _calibrate_s2(K: "Cal3_S2", p):
+    """Cal3_S2::calibrate (gtsam/geometry/Cal3_S2.cpp:53-69)."""
+    fx, fy, s, u0, v0 = K.vector()
+    p = np.asarray(p, dtype=float).reshape(2)
+    y = (p[1] - v0) / fy
+    return np.array([((p[0] - u0) - s * y) / fx, y])
+
+
+def EssentialMatrixFactor(key, pA, pB, model, K: Optional["Cal3_S2"] = None):
+    """EssentialMatrixFactor(key, pA, pB, model[, K]) — :52-78: the points in calibrated coordinates, or in pixels with K
+    (used in the constructor only).  e = vA' E vB."""
+    if K is not None:
+        pA, pB = _calibrate_s2(K, pA), _calibrate_s2(K, pB)
+    return _Factor(A.F_ESSENTIAL, [key], 1, np.concatenate([EssentialMatrix.Homogeneous(pA), EssentialMatrix.Homogeneous(pB)]),
+                   model)
+
+
+def EssentialMatrixFactor2(key1, key2, pA, pB, model, K: Optional["Cal3_S2"] = None):
+    """EssentialMatrixFactor2(key1, key2, pA, pB, model[, K]) — :133-158: key2 is the inverse depth (a double, held as a
+    1-vector); f = 1, or (fx + fy) / 2 with K."""
+    f = 1.0
+    if K is not None:
+        pA, pB = _calibrate_s2(K, pA), _calibrate_s2(K, pB)
+        f = 0.5 * (K.vector()[0] + K.vector()[1])
+    return _Factor(A.F_ESSENTIAL_DEPTH, [key1, key2], 2,
+                   np.concatenate([EssentialMatrix.Homogeneous(pA), np.asarray(pB, dtype=float).reshape(2), [f]]), model)
+
+
+def EssentialMatrixFactor3(key1, key2, pA, pB, cRb: Rot3, model, K: Optional["Cal3_S2"] = None):
+    """EssentialMatrixFactor3(key1, key2, pA, pB, cRb, model[, K]) — :256-273: E is rotated into the camera frame first."""
+    f = EssentialMatrixFactor2(key1, key2, pA, pB, model, K)
+    f.meas = np.concatenate([f.meas, cRb.state()])
+    return f
+
+
+def EssentialMatrixFactor4(keyE, keyK, pA, pB, model=None):
+    """EssentialMatrixFactor4<Cal3_S2>(keyE, keyK, pA, pB, model) — :358-360: the points in pixels, the calibration the
+    variable keyK (a Cal3_S2, held as its 5-vector)."""
+    return _Factor(A.F_ESSENTIAL_CALIB, [keyE, keyK], 1,
+                   np.concatenate([np.asarray(pA, dtype=float).reshape(2), np.asarray(pB, dtype=float).reshape(2)]), model)
+
+
+EssentialMatrixFactor4Cal3_S2 = EssentialMatrixFactor4
+
+
+def EssentialMatrixConstraint(key1, key2, measuredE: "EssentialMatrix", model):
+    """EssentialMatrixConstraint(key1, key2, measuredE, model) — gtsam/slam/EssentialMatrixConstraint.h: between two Pose3."""
+    return _Factor(A.F_ESSENTIAL_CONSTRAINT, [key1, key2], 5, measuredE.state(), model)
+
+
 class Cal3_S2Stereo:
     """gtsam/geometry/Cal3_S2Stereo.h: (fx, fy, s, u0, v0, b)."""
 
@@ -768,7 +955,7 @@ class Values:
         v = self._v[int(key)]
         return v.v.copy() if isinstance(v, _Vector) else v
 
-    atPose2 = atPose3 = atRot3 = atPoint2 = atPoint3 = atVector = at
+    atPose2 = atPose3 = atRot3 = atUnit3 = atEssentialMatrix = atPoint2 = atPoint3 = atVector = at
 
     def dims(self):
         return {k: self._v[k].dim for k in self.keys()}

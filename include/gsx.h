@@ -89,11 +89,28 @@ enum {
   GSX_VAR_POSE3 = 2,  /* state R row-major 9 + t 3, tangent (omega3, v3)       */
   GSX_VAR_CAMERA = 3, /* PinholeCamera<Cal3Bundler>: Pose3 state 12 +          */
                       /* (f,k1,k2,u0,v0); tangent (pose 6, f, k1, k2)          */
-  GSX_VAR_ROT3 = 4    /* Rot3: state R row-major 9, tangent omega 3; retract R Expmap(omega), local
+  GSX_VAR_ROT3 = 4,   /* Rot3: state R row-major 9, tangent omega 3; retract R Expmap(omega), local
                          coordinates Logmap(R1' R2) (gtsam/geometry/Rot3.h:40-47 with GTSAM_ROT3_EXPMAP, the
                          reference's default).  Taken by GSX_F_PRIOR, GSX_F_BETWEEN, GSX_F_ATTITUDE and GSX_F_MAG;
                          the g2o / BAL writers, gsx_initialize_pose3, gsx_lago_*, gsx_triangulate_landmarks and
                          smart factors refuse a problem that holds one (GSX_E_INVALID)                      */
+  GSX_VAR_UNIT3 = 5,  /* Unit3, a point on the unit sphere: state the unit vector p (3), tangent 2 in the basis
+                         B = p.basis() (gtsam/geometry/Unit3.cpp:72-81, 128-138: b1 = normalize(p x axis), the axis
+                         that of the smallest |p_i| with the tie order of CalculateBestAxis, b2 = p x b1).  Retract
+                         Unit3::retract (:255-282: normalize(cos(theta) p + sin(theta) / theta B v), theta = |B v|,
+                         the theta < epsilon branch included), local coordinates Unit3::localCoordinates
+                         (:285-303, with the first-order branch at p . q -> 1 and (pi, 0) at the antipode).  Taken
+                         by GSX_F_PRIOR (and GSX_F_LINEAR); not a group: GSX_F_BETWEEN refuses it by name.  A
+                         state whose norm differs from 1 by more than 1e-9 is refused (gsx_set_values, a prior's
+                         measurement; gsx_update for a new variable): nothing is normalised
+                         silently.  (gsx_solve_gfg / gsx_solve_gfg_h hand a GSX_F_LINEAR-only handle zeros: no state is read)                                       */
+  GSX_VAR_ESSENTIAL = 6 /* EssentialMatrix (gtsam/geometry/EssentialMatrix.h:92-103): state R row-major 9, then
+                         the direction t (3, of unit length as above); tangent omega (3), then the direction's 2.
+                         Retract (R Expmap(omega), t.retract(v)), local coordinates (Logmap(R1' R2),
+                         t1.localCoordinates(t2)).  E = [t]x R is formed where a kernel needs it, never stored.
+                         Taken by GSX_F_PRIOR and the GSX_F_ESSENTIAL* factors; GSX_F_BETWEEN refuses it by name.
+                         Like GSX_VAR_ROT3, both types are refused by the writers, the initializers, lago and
+                         triangulation                                                                      */
 };
 
 /* ---- factor types -------------------------------------------------------- */
@@ -224,12 +241,36 @@ enum {
                                the library once per factor; H = B' (I - q q') (-R [bMeasured]x) in the rotation columns,
                                which is the reference's B' B_q B_q' (-R [b]x) for any basis B_q of q; the translation
                                columns of the POSE3 form are zero                                                       */
-  GSX_F_MAG = 17            /* MagFactor1 (gtsam/navigation/MagFactor.h:121-125): key (ROT3), m = 3; MagPoseFactor<POSE>
+  GSX_F_MAG = 17,           /* MagFactor1 (gtsam/navigation/MagFactor.h:121-125): key (ROT3), m = 3; MagPoseFactor<POSE>
                                (MagPoseFactor.h:74-132): key (POSE3), m = 3, or (POSE2), m = 2.  meas = z, nM, bias, m
                                doubles each, PREPARED: nM = scale * direction.normalized(), z and bias rotated by
                                body_P_sensor where there is one (the constructors do that; the Python classes too).
                                e = R' nM + bias - z; H = [R' nM]x in the rotation columns (Rot3::unrotate), on POSE2
                                (q_y, -q_x) in the theta column (Rot2::unrotate)                                         */
+  /* ---- two-view geometry (gtsam/slam/EssentialMatrixFactor.h, EssentialMatrixConstraint.cpp).  NOT lowered:
+     EssentialMatrixFactor5 (its same-key use lists one variable twice), the Cal3Bundler and Cal3f instantiations of
+     EssentialMatrixFactor4, EssentialTransferFactor, and the Pose3 bearing factors on a Unit3 measurement ---- */
+  GSX_F_ESSENTIAL = 18,     /* EssentialMatrixFactor (:34-106): key (ESSENTIAL); m = 1; meas = vA (3), vB (3), the
+                               homogeneous vectors the factor stores.  e = vA' E vB; H = [vA' E [-vB]x, vA' [-R vB]x B]
+                               with B the direction's basis (EssentialMatrix::error, EssentialMatrix.cpp:104-114)       */
+  GSX_F_ESSENTIAL_DEPTH = 19, /* EssentialMatrixFactor2 (:112-229): keys (ESSENTIAL, VECTOR(1) inverse depth d); m = 2;
+                               meas = dP1 (3), pn (2), f (1).  dP2 = R' (dP1 - d t), e = f (Project(dP2) - pn): d = 0 is
+                               the pure homography, dP2.z <= 0 is projected all the same (PinholeBase::Project has no
+                               cheirality check).  With cRb (9, row-major) appended — 15 doubles — it is
+                               EssentialMatrixFactor3 (:237-317): E is first rotated into the camera frame
+                               (EssentialMatrix::rotate, EssentialMatrix.cpp:73-101), DE multiplied by its 5 x 5 block
+                               [cRb 0; 0 Bq' cRb B], Bq the basis of the ROTATED direction (Rot3::rotate(Unit3))         */
+  GSX_F_ESSENTIAL_CALIB = 20, /* EssentialMatrixFactor4<Cal3_S2> (:334-419): keys (ESSENTIAL, VECTOR(5)), the calibration
+                               (fx, fy, s, u0, v0) as for GSX_F_SFM2; m = 1; meas = pA (2), pB (2) in pixels.  e = vA' E vB
+                               with v = (Cal3_S2::calibrate(p), 1) (gtsam/geometry/Cal3_S2.cpp:53-69, its calibration
+                               Jacobian in HK)                                                                          */
+  GSX_F_ESSENTIAL_CONSTRAINT = 21 /* EssentialMatrixConstraint (EssentialMatrixConstraint.cpp:45-77): keys (POSE3, POSE3);
+                               m = 5; meas = the measured E as R (9) and its direction (3, of unit length to 1e-9).
+                               e = measured.localCoordinates(FromPose3(p1.between(p2))) (EssentialMatrix.cpp:27-45,
+                               Unit3.cpp:44-52); the Jacobians are D_hx_1P2 D_between only — the local-coordinates map
+                               contributes none, as in the reference.  A zero relative translation gives a non-finite
+                               error there and here: it does not trap and surfaces as any other non-finite error does
+                               (a failed factorization / GSX_E_INDETERMINATE, a non-finite gsx_error)                   */
 };
 
 /* ---- noise model kinds (gtsam/linear/NoiseModel.cpp) --------------------- */

@@ -24,6 +24,8 @@
 #include <gtsam/geometry/Cal3Bundler.h>
 #include <gtsam/geometry/Cal3_S2.h>
 #include <gtsam/geometry/Cal3_S2Stereo.h>
+#include <gtsam/geometry/EssentialMatrix.h>
+#include <gtsam/geometry/Unit3.h>
 #include <gtsam/geometry/PinholeCamera.h>
 #include <gtsam/geometry/Pose2.h>
 #include <gtsam/geometry/Pose3.h>
@@ -45,6 +47,8 @@
 #include <gtsam/sam/BearingRangeFactor.h>
 #include <gtsam/sam/RangeFactor.h>
 #include <gtsam/slam/BetweenFactor.h>
+#include <gtsam/slam/EssentialMatrixConstraint.h>
+#include <gtsam/slam/EssentialMatrixFactor.h>
 #include <gtsam/slam/GeneralSFMFactor.h>
 #include <gtsam/slam/ProjectionFactor.h>
 #include <gtsam/slam/StereoFactor.h>
@@ -102,6 +106,14 @@ inline void pack(const gtsam::Rot3& r, std::vector<double>& out) {
   const gtsam::Matrix3 R = r.matrix();
   for (int i = 0; i < 3; ++i)
     for (int c = 0; c < 3; ++c) out.push_back(R(i, c));  // row-major
+}
+inline void pack(const gtsam::Unit3& u, std::vector<double>& out) {
+  const gtsam::Vector3 p = u.unitVector();
+  out.insert(out.end(), {p.x(), p.y(), p.z()});
+}
+inline void pack(const gtsam::EssentialMatrix& E, std::vector<double>& out) {  // R row-major, then the direction
+  pack(E.rotation(), out);
+  pack(E.direction(), out);
 }
 inline void pack(const gtsam::Vector& v, std::vector<double>& out) { out.insert(out.end(), v.data(), v.data() + v.size()); }
 inline void pack(const gtsam::PinholeCamera<gtsam::Cal3Bundler>& c, std::vector<double>& out) {
@@ -234,7 +246,18 @@ inline bool lower_factor(const gtsam::NonlinearFactor::shared_ptr& f, Lowered& L
   } else if (auto ap = std::dynamic_pointer_cast<Pose3AttitudeFactor>(f)) {
     pack(Vector(ap->nRef().unitVector()), m), pack(Vector(ap->bMeasured().unitVector()), m);
     L.add_factor(GSX_F_ATTITUDE, 2, ks, m, kind, np);
+  } else if (auto pu = std::dynamic_pointer_cast<PriorFactor<Unit3>>(f)) {
+    pack(pu->prior(), m), L.add_factor(GSX_F_PRIOR, 2, ks, m, kind, np);
+  } else if (auto pe = std::dynamic_pointer_cast<PriorFactor<EssentialMatrix>>(f)) {
+    pack(pe->prior(), m), L.add_factor(GSX_F_PRIOR, 5, ks, m, kind, np);
+  } else if (auto ec = std::dynamic_pointer_cast<EssentialMatrixConstraint>(f)) {  // keys (pose, pose)
+    pack(ec->measured(), m), L.add_factor(GSX_F_ESSENTIAL_CONSTRAINT, 5, ks, m, kind, np);
   } else {
+    // EssentialMatrixFactor, EssentialMatrixFactor2 / 3 and EssentialMatrixFactor4<Cal3_S2> have device kernels too
+    // (GSX_F_ESSENTIAL, GSX_F_ESSENTIAL_DEPTH, GSX_F_ESSENTIAL_CALIB) but keep vA_ / vB_, dP1_ / pn_ / f_ / cRb_ and pA_ / pB_
+    // private with no accessors (gtsam/slam/EssentialMatrixFactor.h:35, 114-116, 241, 337): a caller that knows the
+    // measurement lowers the factor by hand with lower_essential, lower_essential_depth or lower_essential_calib below;
+    // found in a graph, it stays a GSX_F_LINEAR slot.
     // MagFactor1 and MagPoseFactor<POSE> have device kernels too (GSX_F_MAG) but keep measured_, nM_ and bias_ private with
     // no accessors (gtsam/navigation/MagFactor.h:93-96, MagPoseFactor.h:40-48): a caller that knows them lowers the factor by
     // hand with lower_mag below; found in a graph, it stays a GSX_F_LINEAR slot.
@@ -269,6 +292,37 @@ inline bool lower_mag(const gtsam::NoiseModelFactor& f, const gtsam::Vector& mea
   return true;
 }
 
+// EssentialMatrixFactor given the homogeneous vectors its constructor keeps: (pA, 1) and (pB, 1) in calibrated coordinates
+// (with a calibration K: of K->calibrate(p), EssentialMatrixFactor.h:52-78)
+inline bool lower_essential(const gtsam::NoiseModelFactor& f, const gtsam::Vector3& vA, const gtsam::Vector3& vB, Lowered& L) {
+  int kind;
+  std::vector<double> np;
+  if (!lower_noise(f.noiseModel(), 1, kind, np)) return false;
+  L.add_factor(GSX_F_ESSENTIAL, 1, std::vector<Key>(f.keys().begin(), f.keys().end()),
+               {vA.x(), vA.y(), vA.z(), vB.x(), vB.y(), vB.z()}, kind, np);
+  return true;
+}
+// EssentialMatrixFactor2 given dP1 = (pA, 1), pn = pB (calibrated) and f (1, or (fx + fy) / 2 with a calibration,
+// :133-158); with cRb the EssentialMatrixFactor3 on the same keys (:256-273)
+inline bool lower_essential_depth(const gtsam::NoiseModelFactor& f, const gtsam::Point3& dP1, const gtsam::Point2& pn,
+                                  double focal, Lowered& L, const gtsam::Rot3* cRb = nullptr) {
+  int kind;
+  std::vector<double> np, m{dP1.x(), dP1.y(), dP1.z(), pn.x(), pn.y(), focal};
+  if (!lower_noise(f.noiseModel(), 2, kind, np)) return false;
+  if (cRb) pack(*cRb, m);
+  L.add_factor(GSX_F_ESSENTIAL_DEPTH, 2, std::vector<Key>(f.keys().begin(), f.keys().end()), m, kind, np);
+  return true;
+}
+// EssentialMatrixFactor4<Cal3_S2> given its two pixel measurements (:358-360); keys (E, calibration)
+inline bool lower_essential_calib(const gtsam::NoiseModelFactor& f, const gtsam::Point2& pA, const gtsam::Point2& pB, Lowered& L) {
+  int kind;
+  std::vector<double> np;
+  if (!lower_noise(f.noiseModel(), 1, kind, np)) return false;
+  L.add_factor(GSX_F_ESSENTIAL_CALIB, 1, std::vector<Key>(f.keys().begin(), f.keys().end()), {pA.x(), pA.y(), pB.x(), pB.y()},
+               kind, np);
+  return true;
+}
+
 // variable table + packed Values
 inline void lower_values(const gtsam::Values& values, Lowered& L, std::vector<double>& packed) {
   using namespace gtsam;
@@ -279,6 +333,9 @@ inline void lower_values(const gtsam::Values& values, Lowered& L, std::vector<do
     if (auto p = dynamic_cast<const GenericValue<Pose2>*>(&kv.value)) L.types.push_back(GSX_VAR_POSE2), L.dims.push_back(3), pack(p->value(), packed);
     else if (auto q = dynamic_cast<const GenericValue<Pose3>*>(&kv.value)) L.types.push_back(GSX_VAR_POSE3), L.dims.push_back(6), pack(q->value(), packed);
     else if (auto r3 = dynamic_cast<const GenericValue<Rot3>*>(&kv.value)) L.types.push_back(GSX_VAR_ROT3), L.dims.push_back(3), pack(r3->value(), packed);
+    else if (auto u3 = dynamic_cast<const GenericValue<Unit3>*>(&kv.value)) L.types.push_back(GSX_VAR_UNIT3), L.dims.push_back(2), pack(u3->value(), packed);
+    else if (auto em = dynamic_cast<const GenericValue<EssentialMatrix>*>(&kv.value)) L.types.push_back(GSX_VAR_ESSENTIAL), L.dims.push_back(5), pack(em->value(), packed);
+    else if (auto sc = dynamic_cast<const GenericValue<double>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(1), packed.push_back(sc->value());  // (an inverse depth)
     else if (auto c = dynamic_cast<const GenericValue<PinholeCamera<Cal3Bundler>>*>(&kv.value)) L.types.push_back(GSX_VAR_CAMERA), L.dims.push_back(9), pack(c->value(), packed);
     else if (auto x = dynamic_cast<const GenericValue<Point3>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(3), pack(Vector(x->value()), packed);
     else if (auto y = dynamic_cast<const GenericValue<Point2>*>(&kv.value)) L.types.push_back(GSX_VAR_VECTOR), L.dims.push_back(2), pack(Vector(y->value()), packed);
@@ -308,6 +365,11 @@ inline gtsam::Values unpack_values(const gtsam::Values& like, const std::vector<
     if (dynamic_cast<const GenericValue<Pose2>*>(&kv.value)) out.insert(kv.key, Pose2(packed[o], packed[o + 1], packed[o + 2])), o += 3;
     else if (dynamic_cast<const GenericValue<Pose3>*>(&kv.value)) out.insert(kv.key, pose3(o)), o += 12;
     else if (dynamic_cast<const GenericValue<Rot3>*>(&kv.value)) out.insert(kv.key, rot3(o)), o += 9;
+    else if (dynamic_cast<const GenericValue<Unit3>*>(&kv.value)) out.insert(kv.key, Unit3(packed[o], packed[o + 1], packed[o + 2])), o += 3;
+    else if (dynamic_cast<const GenericValue<EssentialMatrix>*>(&kv.value)) {
+      out.insert(kv.key, EssentialMatrix(rot3(o), Unit3(packed[o + 9], packed[o + 10], packed[o + 11])));
+      o += 12;
+    } else if (dynamic_cast<const GenericValue<double>*>(&kv.value)) out.insert(kv.key, double(packed[o])), o += 1;
     else if (dynamic_cast<const GenericValue<PinholeCamera<Cal3Bundler>>*>(&kv.value)) {
       out.insert(kv.key, PinholeCamera<Cal3Bundler>(pose3(o), Cal3Bundler(packed[o + 12], packed[o + 13], packed[o + 14], packed[o + 15], packed[o + 16])));
       o += 17;
