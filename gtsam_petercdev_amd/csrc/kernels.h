@@ -245,6 +245,27 @@ inline int type_list_of(int t, int vt0, int vt1, long long nmeas) {
   }
   return TL_GENERIC;
 }
+// launch_error holds back one partial-sum slot per list a graph can fill, so that a list of few factors still gets its
+// block.  The lists came in groups; the count is the end of the newest group that has a factor, so a graph keeps the
+// shares — hence the summation order, hence the bits — that it had before later lists existed.
+constexpr int kListGroupEnds[] = {TL_PROJECTION_SENSOR, TL_SMART, TL_TRANSLATION, TL_ABSOLUTE, TL_ESSENTIAL, kNumTypeLists};
+constexpr int held_slots(const int counts[kNumTypeLists]) {
+  int held = kListGroupEnds[0];
+  for (int g = 1; g < (int)(sizeof(kListGroupEnds) / sizeof(kListGroupEnds[0])); ++g)
+    for (int k = kListGroupEnds[g - 1]; k < kListGroupEnds[g]; ++k)
+      if (counts[k] > 0) held = kListGroupEnds[g];
+  return held;
+}
+constexpr int held_slots_with(int a, int b = TL_SFM) {  // of a graph with factors in the lists a and b
+  int counts[kNumTypeLists] = {};
+  counts[a] = counts[b] = 1;
+  return held_slots(counts);
+}
+static_assert(held_slots_with(TL_STEREO) == TL_PROJECTION_SENSOR && held_slots_with(TL_SFM2) == TL_SMART &&
+                  held_slots_with(TL_SMART) == TL_TRANSLATION && held_slots_with(TL_BATA) == TL_ABSOLUTE &&
+                  held_slots_with(TL_GPS_CALIB, TL_TRANSLATION) == TL_ESSENTIAL &&
+                  held_slots_with(TL_PRIOR_UNIT3, TL_ABSOLUTE) == kNumTypeLists && held_slots_with(TL_ESSENTIAL, TL_SMART) == kNumTypeLists,
+              "the slots the nested conditional of launch_error held back, situation by situation");
 // The state of the smart projection factors of a handle (smart.hip), per smart factor in graph order ("slot"): the cameras
 // of the call in progress, and the re-triangulation cache of SmartProjectionFactor::decideIfTriangulate — the camera poses
 // of the last triangulation, its point and its status (-1: never triangulated).

@@ -15,9 +15,11 @@
 // upper-triangular [R S d] (gtsam/linear/GaussianConditional.h:243-252), the rhs d is the last ROW.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "device_geometry.h"
 #include "gsx_internal.h"
@@ -211,7 +213,58 @@ __device__ inline void local_coords(int type, int dim, const double* x, const do
 // ---------------------------------------------------------------------------------------------
 // linearize: one thread per factor (register-resident [A b], whitening fused)
 // ---------------------------------------------------------------------------------------------
-// GeneralSFMFactor::linearize — gtsam/slam/GeneralSFMFactor.h:141-177
+// A family's residual is written ONCE, in its evaluator `<family>_eval<..., WITH_H>(P, f, fr, values, e, H)`: the
+// unwhitened e (M) and, WITH_H, H (row-major M x D, the keys' tangent columns one after the other).  The linearize kernel
+// of the family stores [A b] = [H, -e] whitened; its error kernel is the shell below.  The four projecting families (SFM,
+// SFM2, projection, stereo) are the exception: their linearize kernels keep a residual of their own, for the reasons at
+// sfm_residual and projection_residual, and `<family>_residual` serves the error side alone.
+template <int M, int D>
+__device__ __forceinline__ void store_linearized(const double (&e)[M], const double* H, const FactorRec& fr,
+                                                 const DevProblem& P, double* jac) {
+  double J[M * (D + 1)];
+#pragma unroll
+  for (int c = 0; c < D; ++c)
+#pragma unroll
+    for (int r = 0; r < M; ++r) J[c * M + r] = H[r * D + c];
+#pragma unroll
+  for (int r = 0; r < M; ++r) J[D * M + r] = -e[r];
+  whiten_store<M, D + 1>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+// the error kernel of a family with M rows: its evaluator without H, the partial sums in block order
+template <int M, auto EVAL>
+__global__ void __launch_bounds__(256) error_family_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                           double* partials) {
+  double acc = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int f = list[i];
+    const FactorRec fr = P.frec[f];
+    const int kind = (fr.type_kind >> 8) & 0xffff;
+    const double* np = P.noise + fr.noise_off;
+    double e[M];
+    EVAL(P, f, fr, values, e, nullptr);
+    acc += whitened_half_sqnorm<M>(e, kind, np);
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// GeneralSFMFactor::linearize — gtsam/slam/GeneralSFMFactor.h:141-177; behind the camera: zero Jacobians, zero error.
+// NOT one evaluator: the compiler fuses multiply-adds per basic block, so Jacobians drawn from a shared evaluator differ
+// from today's in the last bit (seen: 1 ulp of the largest entries), and this kernel is on the benchmark's path — the
+// linearize kernel keeps its own copy of the residual (so does GeneralSFMFactor2 below)
+__device__ __forceinline__ void sfm_residual(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                             double (&e)[2], double*) {
+  const double* cam = values + fr.s0;
+  const double* pt = values + fr.s1;
+  const double* z = P.meas + fr.meas_off;
+  double camr[17], ptr3[3], pi[2];
+#pragma unroll
+  for (int k = 0; k < 17; ++k) camr[k] = cam[k];
+  ptr3[0] = pt[0]; ptr3[1] = pt[1]; ptr3[2] = pt[2];
+  const bool ok = sfm_project(camr, ptr3, pi, nullptr, nullptr);
+  e[0] = ok ? pi[0] - z[0] : 0.0;
+  e[1] = ok ? pi[1] - z[1] : 0.0;
+}
 // (defined below) priors and other rare factors ride in the first blocks of the launch of a main factor family
 // (launch_linearize): a launch of their own is pure latency — 22 us for the 1 723 camera priors of BAL-1723
 __device__ __forceinline__ void linearize_generic_body(const DevProblem& P, const int* list, int n, const double* values,
@@ -256,35 +309,66 @@ __global__ void __launch_bounds__(256) linearize_sfm_kernel(DevProblem P, const 
   whiten_store<2, 13>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
 }
 
-// BearingRangeFactor<Pose2,Point2> — gtsam/sam/BearingRangeFactor.h (ExpressionFactor: e = -Local(h(x), z))
-__global__ void __launch_bounds__(256) linearize_bearingrange_kernel(DevProblem P, const int* list, int n,
-                                                                     const double* values, double* jac) {
+// BearingRangeFactor<Pose2,Point2> — gtsam/sam/BearingRangeFactor.h (ExpressionFactor: e = Local(z, h(x)));
+// BearingFactor<Pose2,Point2> — gtsam/sam/BearingFactor.h — is its bearing row (M = 1)
+template <int M, bool WITH_H>
+__device__ __forceinline__ void bearing_range_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                                   double (&e)[M], double* H) {
+  const double* pose = values + fr.s0;
+  const double* pt = values + fr.s1;
+  const double* z = P.meas + fr.meas_off;
+  double ps[3] = {pose[0], pose[1], pose[2]}, p2[2] = {pt[0], pt[1]}, br[2], H1[6], H2[4];
+  bearing_range_2d(ps, p2, br, WITH_H ? H1 : nullptr, WITH_H ? H2 : nullptr);
+  e[0] = wrap_angle(br[0] - z[0]);
+  if constexpr (M == 2) e[1] = br[1] - z[1];
+  if constexpr (WITH_H) {
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+      H[5 * r] = H1[3 * r]; H[5 * r + 1] = H1[3 * r + 1]; H[5 * r + 2] = H1[3 * r + 2];
+      H[5 * r + 3] = H2[2 * r]; H[5 * r + 4] = H2[2 * r + 1];
+    }
+  }
+}
+template <int M>
+__global__ void __launch_bounds__(256) linearize_bearing_range_kernel(DevProblem P, const int* list, int n,
+                                                                      const double* values, double* jac) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int f = list[i];
-  const int kp = P.f_key_ptr[f];
-  const double* pose = values + P.var_state_off[P.f_vars[kp]];
-  const double* pt = values + P.var_state_off[P.f_vars[kp + 1]];
-  const double* z = P.meas + P.f_meas_off[f];
-  double ps[3] = {pose[0], pose[1], pose[2]}, p2[2] = {pt[0], pt[1]}, br[2], H1[6], H2[4], J[12];
-  bearing_range_2d(ps, p2, br, H1, H2);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    J[2 * c] = H1[c];
-    J[2 * c + 1] = H1[3 + c];
-  }
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    J[6 + 2 * c] = H2[c];
-    J[6 + 2 * c + 1] = H2[2 + c];
-  }
-  J[10] = -wrap_angle(br[0] - z[0]);
-  J[11] = -(br[1] - z[1]);
-  whiten_store<2, 6>(J, P.f_noise_kind[f], P.noise + P.f_noise_off[f], jac + P.f_jac_off[f]);
+  const FactorRec fr = P.frec[f];
+  double e[M], H[M * 5];
+  bearing_range_eval<M, true>(P, f, fr, values, e, H);
+  store_linearized<M, 5>(e, H, fr, P, jac);
 }
 
 // GenericProjectionFactor<Pose3,Point3,Cal3_S2>::evaluateError — gtsam/slam/ProjectionFactor.h:138-166; SENSOR: its
-// if(body_P_sensor_) branch (the sensor pose follows the 7 measurement doubles), the camera at pose * body_P_sensor
+// if(body_P_sensor_) branch (the sensor pose follows the 7 measurement doubles), the camera at pose * body_P_sensor.
+// Behind the camera: zero Jacobians, error (2 fx, 2 fx).
+// NOT one evaluator: with the Jacobians drawn from a shared one the plain linearize kernel takes 74 VGPRs for 70 and
+// occupancy 6 for 7 (stereo: 84 for 80, 5 for 6), so the linearize kernel keeps its own copy of the residual.  It also
+// keeps its walk through the per-factor arrays: with nothing changed but its loads going through the record (jac_off,
+// noise_off and type_kind then live across the projection) it measures 74 VGPRs for 70, occupancy 6 for 7 — 70 is 2 below
+// the 72-VGPR step — and the SENSOR form 110 for 106.  Occupancy is not traded for tidiness
+template <bool SENSOR>
+__device__ __forceinline__ void projection_residual(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                                    double (&e)[2], double*) {
+  const double* pose = values + fr.s0;
+  const double* pt = values + fr.s1;
+  const double* z = P.meas + fr.meas_off;  // u v fx fy s u0 v0
+  double pr[12], p3[3], K[5], pi[2];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) pr[k] = pose[k];
+  p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) K[k] = z[2 + k];
+  if constexpr (SENSOR) pose3_compose_sensor(pr, z + 7);
+  if (pinhole_project_s2(pr, p3, K, pi, nullptr, nullptr)) {
+    e[0] = pi[0] - z[0];
+    e[1] = pi[1] - z[1];
+  } else {
+    e[0] = e[1] = 2.0 * K[0];
+  }
+}
 template <bool SENSOR>
 __global__ void __launch_bounds__(256) linearize_projection_kernel(DevProblem P, const int* list, int n, const double* values,
                                                                    double* jac, DevStatus* status) {
@@ -328,7 +412,27 @@ __global__ void __launch_bounds__(256) linearize_projection_kernel(DevProblem P,
   whiten_store<2, 10>(J, P.f_noise_kind[f], P.noise + P.f_noise_off[f], jac + P.f_jac_off[f]);
 }
 
-// BetweenFactor<Pose2> via NoiseModelFactor::linearize — gtsam/nonlinear/NonlinearFactor.cpp:152-184
+// BetweenFactor<Pose2> via NoiseModelFactor::linearize — gtsam/nonlinear/NonlinearFactor.cpp:152-184: h = x1^-1 x2,
+// e = Local(z, h); Ad(h^-1) = [[c,-s,y],[s,c,-x],[0,0,1]] of hi = h^-1, H1 = -Ad, H2 = I
+template <bool WITH_H>
+__device__ __forceinline__ void between_pose2_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                                   double (&e)[3], double* H) {
+  const P2 x1 = load_pose2(values + fr.s0);
+  const P2 x2 = load_pose2(values + fr.s1);
+  const P2 h = compose(inverse(x1), x2);
+  const P2 zh = compose(inverse(load_pose2(P.meas + fr.meas_off)), h);
+  e[0] = zh.x; e[1] = zh.y; e[2] = theta(zh);
+  if constexpr (WITH_H) {
+    const P2 hi = inverse(h);
+    H[0] = -hi.c; H[1] = hi.s; H[2] = -hi.y;
+    H[6] = -hi.s; H[7] = -hi.c; H[8] = hi.x;
+    H[12] = 0; H[13] = 0; H[14] = -1;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) H[6 * r + 3 + c] = (r == c) ? 1.0 : 0.0;
+  }
+}
 __global__ void __launch_bounds__(256) linearize_between_pose2_kernel(DevProblem P, const int* list, int n,
                                                                       const double* values, double* jac, const int* glist,
                                                                       int gn) {
@@ -341,23 +445,32 @@ __global__ void __launch_bounds__(256) linearize_between_pose2_kernel(DevProblem
   if (i >= n) return;
   const int f = list[i];
   const FactorRec fr = P.frec[f];
-  const P2 x1 = load_pose2(values + fr.s0);
-  const P2 x2 = load_pose2(values + fr.s1);
-  const P2 h = compose(inverse(x1), x2);
-  const P2 zh = compose(inverse(load_pose2(P.meas + fr.meas_off)), h);
-  const P2 hi = inverse(h);
-  // Ad(h^-1) = [[c,-s,y],[s,c,-x],[0,0,1]]; A1 = -Ad, A2 = I, b = -e
-  double J[21];
-  J[0] = -hi.c; J[1] = -hi.s; J[2] = 0;
-  J[3] = hi.s; J[4] = -hi.c; J[5] = 0;
-  J[6] = -hi.y; J[7] = hi.x; J[8] = -1;
-  J[9] = 1; J[10] = 0; J[11] = 0;
-  J[12] = 0; J[13] = 1; J[14] = 0;
-  J[15] = 0; J[16] = 0; J[17] = 1;
-  J[18] = -zh.x; J[19] = -zh.y; J[20] = -theta(zh);
-  whiten_store<3, 7>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+  double e[3], H[18];
+  between_pose2_eval<true>(P, f, fr, values, e, H);
+  store_linearized<3, 6>(e, H, fr, P, jac);
 }
 
+// BetweenFactor<Pose3>: e = Logmap(z^-1 h), H1 = -Ad(h^-1), H2 = I (the identity for the Local derivative)
+template <bool WITH_H>
+__device__ __forceinline__ void between_pose3_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                                   double (&e)[6], double* H) {
+  const P3 x1 = load_pose3(values + fr.s0);
+  const P3 x2 = load_pose3(values + fr.s1);
+  const P3 h = between(x1, x2);
+  const P3 zh = compose(inverse(load_pose3(P.meas + fr.meas_off)), h);
+  pose3_logmap(zh, e);
+  if constexpr (WITH_H) {
+    double Ad[36];
+    pose3_adjoint(inverse(h), Ad);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        H[12 * r + c] = -Ad[6 * r + c];
+        H[12 * r + 6 + c] = (r == c) ? 1.0 : 0.0;
+      }
+  }
+}
 __global__ void __launch_bounds__(256) linearize_between_pose3_kernel(DevProblem P, const int* list, int n,
                                                                       const double* values, double* jac, const int* glist,
                                                                       int gn) {
@@ -370,23 +483,9 @@ __global__ void __launch_bounds__(256) linearize_between_pose3_kernel(DevProblem
   if (i >= n) return;
   const int f = list[i];
   const FactorRec fr = P.frec[f];
-  const P3 x1 = load_pose3(values + fr.s0);
-  const P3 x2 = load_pose3(values + fr.s1);
-  const P3 h = between(x1, x2);
-  const P3 zh = compose(inverse(load_pose3(P.meas + fr.meas_off)), h);
-  double e[6], Ad[36], J[78];
-  pose3_logmap(zh, e);
-  pose3_adjoint(inverse(h), Ad);
-#pragma unroll
-  for (int c = 0; c < 6; ++c)
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      J[c * 6 + r] = -Ad[6 * r + c];
-      J[36 + c * 6 + r] = (r == c) ? 1.0 : 0.0;
-    }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) J[72 + r] = -e[r];
-  whiten_store<6, 13>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+  double e[6], H[72];
+  between_pose3_eval<true>(P, f, fr, values, e, H);
+  store_linearized<6, 12>(e, H, fr, P, jac);
 }
 
 // priors of every type and BetweenFactor on vector spaces: rare, runtime dims, built in place
@@ -424,81 +523,94 @@ __global__ void linearize_generic_kernel(DevProblem P, const int* list, int n, c
   linearize_generic_body(P, list, n, values, jac, blockIdx.x);
 }
 
-// RangeFactor<A1,A2> — gtsam/sam/RangeFactor.h (ExpressionFactor: e = range(a1, a2) - z, b = -e); V1 = POSE2 | POSE3,
+// RangeFactor<A1,A2> — gtsam/sam/RangeFactor.h (ExpressionFactor: e = range(a1, a2) - z); V1 = POSE2 | POSE3,
 // V2 = VECTOR (a point of the pose's space) or V1 (a second pose: the range to its translation).  One row:
-// [A b] is 1 x (d1 + d2 + 1).
+// H is 1 x (d1 + d2).
 // SENSOR: RangeFactorWithTransform (RangeFactor.h:104-150) — body_T_sensor follows the range in the measurement, in the
 // state layout of V1; the range is taken from a1 * body_T_sensor.
+template <int V1, int V2>
+constexpr int kRangeD = (V1 == GSX_VAR_POSE2 ? 3 : 6) + (V2 == GSX_VAR_VECTOR ? (V1 == GSX_VAR_POSE2 ? 2 : 3) : (V1 == GSX_VAR_POSE2 ? 3 : 6));
+template <int V1, int V2, bool SENSOR, bool WITH_H>
+__device__ __forceinline__ void range_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                           double (&e)[1], double* H) {
+  const double* a1 = values + fr.s0;
+  const double* a2 = values + fr.s1;
+  const double* z = P.meas + fr.meas_off;
+  if constexpr (V1 == GSX_VAR_POSE2) {
+    double ps[3] = {a1[0], a1[1], a1[2]}, p2[2] = {a2[0], a2[1]}, H1[3], Dd[2];
+    if constexpr (SENSOR) {
+      e[0] = range_2d_cs(pose2_compose_sensor(ps, z + 1), p2, WITH_H ? H1 : nullptr, WITH_H ? Dd : nullptr) - z[0];
+      if constexpr (WITH_H) row_times_sensor_adjoint2(H1, z + 1);
+    } else {
+      e[0] = range_2d(ps, p2, WITH_H ? H1 : nullptr, WITH_H ? Dd : nullptr) - z[0];
+    }
+    if constexpr (WITH_H) {
+      H[0] = H1[0]; H[1] = H1[1]; H[2] = H1[2];
+      if constexpr (V2 == GSX_VAR_POSE2) {  // D d / D other = [R_other 0] (Pose2.cpp:302-308)
+        const double c2 = cos(a2[2]), s2 = sin(a2[2]);
+        H[3] = Dd[0] * c2 + Dd[1] * s2; H[4] = -Dd[0] * s2 + Dd[1] * c2; H[5] = 0.0;
+      } else {
+        H[3] = Dd[0]; H[4] = Dd[1];
+      }
+    }
+  } else {
+    constexpr int TO = (V2 == GSX_VAR_POSE3) ? 9 : 0;  // where the other variable's translation sits in its state
+    double pr[12], p3[3] = {a2[TO], a2[TO + 1], a2[TO + 2]}, H1[6], H2[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pr[k] = a1[k];
+    if constexpr (SENSOR) pose3_compose_sensor(pr, z + 1);
+    e[0] = range_3d(pr, p3, WITH_H ? H1 : nullptr, WITH_H ? H2 : nullptr) - z[0];
+    if constexpr (WITH_H) {
+      if constexpr (SENSOR) row_times_sensor_adjoint(H1, z + 1);
+#pragma unroll
+      for (int c = 0; c < 6; ++c) H[c] = H1[c];
+      if constexpr (V2 == GSX_VAR_POSE3) {  // [0 0 0, D_local_point R_other] (Pose3.cpp:425-431)
+        H[6] = H[7] = H[8] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) H[9 + c] = H2[0] * a2[c] + H2[1] * a2[3 + c] + H2[2] * a2[6 + c];
+      } else {
+        H[6] = H2[0]; H[7] = H2[1]; H[8] = H2[2];
+      }
+    }
+  }
+}
 template <int V1, int V2, bool SENSOR>
 __global__ void __launch_bounds__(256) linearize_range_kernel(DevProblem P, const int* list, int n, const double* values,
                                                               double* jac) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const FactorRec fr = P.frec[list[i]];
-  const double* a1 = values + fr.s0;
-  const double* a2 = values + fr.s1;
-  const double z = P.meas[fr.meas_off];
-  if constexpr (V1 == GSX_VAR_POSE2) {
-    constexpr int NC = (V2 == GSX_VAR_POSE2) ? 7 : 6;
-    double ps[3] = {a1[0], a1[1], a1[2]}, p2[2] = {a2[0], a2[1]}, H1[3], Dd[2], J[NC];
-    double r;
-    if constexpr (SENSOR) {
-      r = range_2d_cs(pose2_compose_sensor(ps, P.meas + fr.meas_off + 1), p2, H1, Dd);
-      row_times_sensor_adjoint2(H1, P.meas + fr.meas_off + 1);
-    } else {
-      r = range_2d(ps, p2, H1, Dd);
-    }
-    J[0] = H1[0]; J[1] = H1[1]; J[2] = H1[2];
-    if constexpr (V2 == GSX_VAR_POSE2) {  // D d / D other = [R_other 0] (Pose2.cpp:302-308)
-      const double c2 = cos(a2[2]), s2 = sin(a2[2]);
-      J[3] = Dd[0] * c2 + Dd[1] * s2; J[4] = -Dd[0] * s2 + Dd[1] * c2; J[5] = 0.0;
-    } else {
-      J[3] = Dd[0]; J[4] = Dd[1];
-    }
-    J[NC - 1] = -(r - z);
-    whiten_store<1, NC>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
-  } else {
-    constexpr int NC = (V2 == GSX_VAR_POSE3) ? 13 : 10;
-    constexpr int TO = (V2 == GSX_VAR_POSE3) ? 9 : 0;  // where the other variable's translation sits in its state
-    double pr[12], p3[3] = {a2[TO], a2[TO + 1], a2[TO + 2]}, H1[6], H2[3], J[NC];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pr[k] = a1[k];
-    if constexpr (SENSOR) pose3_compose_sensor(pr, P.meas + fr.meas_off + 1);
-    const double r = range_3d(pr, p3, H1, H2);
-    if constexpr (SENSOR) row_times_sensor_adjoint(H1, P.meas + fr.meas_off + 1);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) J[c] = H1[c];
-    if constexpr (V2 == GSX_VAR_POSE3) {  // [0 0 0, D_local_point R_other] (Pose3.cpp:425-431)
-      J[6] = J[7] = J[8] = 0.0;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) J[9 + c] = H2[0] * a2[c] + H2[1] * a2[3 + c] + H2[2] * a2[6 + c];
-    } else {
-      J[6] = H2[0]; J[7] = H2[1]; J[8] = H2[2];
-    }
-    J[NC - 1] = -(r - z);
-    whiten_store<1, NC>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
-  }
-}
-
-// BearingFactor<Pose2,Point2> — gtsam/sam/BearingFactor.h: the bearing row of BearingRangeFactor
-__global__ void __launch_bounds__(256) linearize_bearing_kernel(DevProblem P, const int* list, int n, const double* values,
-                                                                double* jac) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const FactorRec fr = P.frec[list[i]];
-  const double* pose = values + fr.s0;
-  const double* pt = values + fr.s1;
-  double ps[3] = {pose[0], pose[1], pose[2]}, p2[2] = {pt[0], pt[1]}, br[2], H1[6], H2[4], J[6];
-  bearing_range_2d(ps, p2, br, H1, H2);
-  J[0] = H1[0]; J[1] = H1[1]; J[2] = H1[2];
-  J[3] = H2[0]; J[4] = H2[1];
-  J[5] = -wrap_angle(br[0] - P.meas[fr.meas_off]);
-  whiten_store<1, 6>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+  const int f = list[i];
+  const FactorRec fr = P.frec[f];
+  double e[1], H[kRangeD<V1, V2>];
+  range_eval<V1, V2, SENSOR, true>(P, f, fr, values, e, H);
+  store_linearized<1, kRangeD<V1, V2>>(e, H, fr, P, jac);
 }
 
 // GenericStereoFactor<Pose3,Point3>::evaluateError — gtsam/slam/StereoFactor.h:126-154; SENSOR: its if(body_P_sensor_)
 // branch (the sensor pose follows the 9 measurement doubles).  The adjoint is applied a row at a time (two rotations and a
-// cross product on the six doubles of the row), never as a 6 x 6 matrix: no registers beyond the row's own
+// cross product on the six doubles of the row), never as a 6 x 6 matrix: no registers beyond the row's own.  Behind the
+// camera: zero Jacobians, error (2 fx, 2 fx, 2 fx)
+// (not one evaluator with the linearize kernel: see projection_residual)
+template <bool SENSOR>
+__device__ __forceinline__ void stereo_residual(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                                double (&e)[3], double*) {
+  const double* pose = values + fr.s0;
+  const double* pt = values + fr.s1;
+  const double* z = P.meas + fr.meas_off;  // uL uR v fx fy s u0 v0 b
+  double pr[12], p3[3], K[6], pi[3];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) pr[k] = pose[k];
+  p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) K[k] = z[3 + k];
+  if constexpr (SENSOR) pose3_compose_sensor(pr, z + 9);
+  if (stereo_project(pr, p3, K, pi, nullptr, nullptr)) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) e[r] = pi[r] - z[r];
+  } else {
+    e[0] = e[1] = e[2] = 2.0 * K[0];
+  }
+}
 template <bool SENSOR>
 __global__ void __launch_bounds__(256) linearize_stereo_kernel(DevProblem P, const int* list, int n, const double* values,
                                                                double* jac, DevStatus* status) {
@@ -539,8 +651,25 @@ __global__ void __launch_bounds__(256) linearize_stereo_kernel(DevProblem P, con
   whiten_store<3, 10>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
 }
 
-// GeneralSFMFactor2<Cal3_S2>::evaluateError — gtsam/slam/GeneralSFMFactor.h:264-278: keys (pose, point, K); [A b] is
-// 2 x (6 + 3 + 5 + 1).  Cheirality: zero Jacobians and a zero error (:270-277)
+// GeneralSFMFactor2<Cal3_S2>::evaluateError — gtsam/slam/GeneralSFMFactor.h:264-278: keys (pose, point, K); H is
+// 2 x (6 + 3 + 5).  Cheirality: zero Jacobians and a zero error (:270-277)
+// (not one evaluator with the linearize kernel: see sfm_residual)
+__device__ __forceinline__ void sfm2_residual(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                              double (&e)[2], double*) {
+  const double* pose = values + fr.s0;
+  const double* pt = values + fr.s1;
+  const double* cal = values + P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]];  // (the record holds two state offsets)
+  const double* z = P.meas + fr.meas_off;
+  double pr[12], p3[3], K[5], pi[2];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) pr[k] = pose[k];
+  p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) K[k] = cal[k];
+  const bool ok = pinhole_project_s2(pr, p3, K, pi, nullptr, nullptr);
+  e[0] = ok ? pi[0] - z[0] : 0.0;
+  e[1] = ok ? pi[1] - z[1] : 0.0;
+}
 __global__ void __launch_bounds__(256) linearize_sfm2_kernel(DevProblem P, const int* list, int n, const double* values,
                                                              double* jac, DevStatus* status) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -585,56 +714,73 @@ __global__ void __launch_bounds__(256) linearize_sfm2_kernel(DevProblem P, const
 
 // TranslationFactor::evaluateError — gtsam/sfm/TranslationFactor.h:68-78: e = normalize(Tb - Ta) - z with the derivative
 // of normalize (gtsam/geometry/Point3.cpp:52-62), H1 = -H2.  Ta == Tb divides by zero, as there: no special case
-__global__ void __launch_bounds__(256) linearize_translation_kernel(DevProblem P, const int* list, int n, const double* values,
-                                                                    double* jac) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const FactorRec fr = P.frec[list[i]];
+template <bool WITH_H>
+__device__ __forceinline__ void translation_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                                 double (&e)[3], double* H) {
   const double* ta = values + fr.s0;
   const double* tb = values + fr.s1;
   const double* z = P.meas + fr.meas_off;
   const double x = tb[0] - ta[0], y = tb[1] - ta[1], w = tb[2] - ta[2];
-  const double x2 = x * x, y2 = y * y, z2 = w * w, n2 = x2 + y2 + z2, nrm = sqrt(n2), n3 = n2 * nrm;
-  double H[9] = {(y2 + z2) / n3, -(x * y) / n3, -(x * w) / n3, 0, (x2 + z2) / n3, -(y * w) / n3, 0, 0, (x2 + y2) / n3}, J[21];
-  H[3] = H[1]; H[6] = H[2]; H[7] = H[5];
+  const double x2 = x * x, y2 = y * y, z2 = w * w, n2 = x2 + y2 + z2, nrm = sqrt(n2);
+  e[0] = x / nrm - z[0];
+  e[1] = y / nrm - z[1];
+  e[2] = w / nrm - z[2];
+  if constexpr (WITH_H) {
+    const double n3 = n2 * nrm;
+    double D[9] = {(y2 + z2) / n3, -(x * y) / n3, -(x * w) / n3, 0, (x2 + z2) / n3, -(y * w) / n3, 0, 0, (x2 + y2) / n3};
+    D[3] = D[1]; D[6] = D[2]; D[7] = D[5];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) {  // (symmetric: row- and column-major agree)
-    J[k] = -H[k];
-    J[9 + k] = H[k];
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        H[6 * r + c] = -D[3 * r + c];
+        H[6 * r + 3 + c] = D[3 * r + c];
+      }
   }
-  J[18] = z[0] - x / nrm;  // b = -e
-  J[19] = z[1] - y / nrm;
-  J[20] = z[2] - w / nrm;
-  whiten_store<3, 7>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+}
+__global__ void __launch_bounds__(256) linearize_translation_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                    double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int f = list[i];
+  const FactorRec fr = P.frec[f];
+  double e[3], H[18];
+  translation_eval<true>(P, f, fr, values, e, H);
+  store_linearized<3, 6>(e, H, fr, P, jac);
 }
 
 // BilinearAngleTranslationFactor::evaluateError — gtsam/sfm/TranslationFactor.h:133-149: keys (Ta, Tb, scale); e =
 // |s| (Tb - Ta) - z, H1 = -|s| I, H2 = |s| I, H3 = Tb - Ta for s >= 0 (zero included), else Ta - Tb
+template <bool WITH_H>
+__device__ __forceinline__ void bata_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                          double (&e)[3], double* H) {
+  const double* ta = values + fr.s0;
+  const double* tb = values + fr.s1;
+  const double s = values[P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]]];  // (the record holds two state offsets)
+  const double* z = P.meas + fr.meas_off;
+  const double a = fabs(s), d[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    e[r] = d[r] * a - z[r];
+    if constexpr (WITH_H) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        H[7 * r + c] = (r == c) ? -a : 0.0;
+        H[7 * r + 3 + c] = (r == c) ? a : 0.0;
+      }
+      H[7 * r + 6] = s >= 0 ? d[r] : -d[r];
+    }
+  }
+}
 __global__ void __launch_bounds__(256) linearize_bata_kernel(DevProblem P, const int* list, int n, const double* values,
                                                              double* jac) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int f = list[i];
   const FactorRec fr = P.frec[f];
-  const double* ta = values + fr.s0;
-  const double* tb = values + fr.s1;
-  const double s = values[P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]]];  // (the record holds two state offsets)
-  const double* z = P.meas + fr.meas_off;
-  const double a = fabs(s), d[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
-  double J[24];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      J[3 * c + r] = (r == c) ? -a : 0.0;
-      J[9 + 3 * c + r] = (r == c) ? a : 0.0;
-    }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    J[18 + r] = s >= 0 ? d[r] : -d[r];
-    J[21 + r] = z[r] - d[r] * a;  // b = -e
-  }
-  whiten_store<3, 8>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+  double e[3], H[21];
+  bata_eval<true>(P, f, fr, values, e, H);
+  store_linearized<3, 7>(e, H, fr, P, jac);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -818,38 +964,46 @@ __global__ void __launch_bounds__(256) error_absolute_kernel(DevProblem P, const
 
 // GPSFactorArmCalib (GPSFactor.cpp:113-128): keys (POSE3, VECTOR(3)), the lever arm a variable; e = t + R bL - nT,
 // H1 = [-R [bL]x, R], H2 = R
+template <bool WITH_H>
+__device__ __forceinline__ void gps_calib_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                               double (&e)[3], double* H) {
+  const double* x = values + fr.s0;
+  const double* z = P.meas + fr.meas_off;
+  const double b[3] = {values[fr.s1], values[fr.s1 + 1], values[fr.s1 + 2]};
+  double R[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = x[k];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) e[r] = (x[9 + r] + (R[3 * r] * b[0] + R[3 * r + 1] * b[1] + R[3 * r + 2] * b[2])) - z[r];
+  if constexpr (WITH_H) {
+    double G[9];
+    neg_R_skew(R, b, G);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        H[9 * r + c] = G[3 * r + c];
+        H[9 * r + 3 + c] = R[3 * r + c];
+        H[9 * r + 6 + c] = R[3 * r + c];
+      }
+  }
+}
 __global__ void __launch_bounds__(256) linearize_gps_calib_kernel(DevProblem P, const int* list, int n, const double* values,
                                                                   double* jac) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const FactorRec fr = P.frec[list[i]];
-  const double* x = values + fr.s0;
-  const double* z = P.meas + fr.meas_off;
-  const double b[3] = {values[fr.s1], values[fr.s1 + 1], values[fr.s1 + 2]};
-  double R[9], G[9], J[30];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = x[k];
-  neg_R_skew(R, b, G);
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      J[3 * c + r] = G[3 * r + c];
-      J[9 + 3 * c + r] = R[3 * r + c];
-      J[18 + 3 * c + r] = R[3 * r + c];
-    }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) J[27 + r] = -((x[9 + r] + (R[3 * r] * b[0] + R[3 * r + 1] * b[1] + R[3 * r + 2] * b[2])) - z[r]);
-  whiten_store<3, 10>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+  const int f = list[i];
+  const FactorRec fr = P.frec[f];
+  double e[3], H[27];
+  gps_calib_eval<true>(P, f, fr, values, e, H);
+  store_linearized<3, 9>(e, H, fr, P, jac);
 }
 
 // BetweenFactor<Rot3> (BetweenFactor.h:111-124) with the identity for the Local derivative, as the Pose3 kernel has it:
-// h = R1' R2, e = Logmap(z' h), A1 = -h' = -R2' R1, A2 = I
-__global__ void __launch_bounds__(256) linearize_between_rot3_kernel(DevProblem P, const int* list, int n, const double* values,
-                                                                     double* jac) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const FactorRec fr = P.frec[list[i]];
+// h = R1' R2, e = Logmap(z' h), H1 = -h' = -R2' R1, H2 = I
+template <bool WITH_H>
+__device__ __forceinline__ void between_rot3_eval(const DevProblem& P, int f, const FactorRec& fr, const double* values,
+                                                  double (&e)[3], double* H) {
   M3 R1, R2, Z;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
@@ -859,16 +1013,26 @@ __global__ void __launch_bounds__(256) linearize_between_rot3_kernel(DevProblem 
   }
   const M3 h = mul(transpose(R1), R2);
   const V3 w = so3_logmap(mul(transpose(Z), h));
-  double J[21];
+  e[0] = w.x; e[1] = w.y; e[2] = w.z;
+  if constexpr (WITH_H) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      J[3 * c + r] = -h.a[3 * c + r];  // (-h')(r, c)
-      J[9 + 3 * c + r] = (r == c) ? 1.0 : 0.0;
-    }
-  J[18] = -w.x; J[19] = -w.y; J[20] = -w.z;
-  whiten_store<3, 7>(J, (fr.type_kind >> 8) & 0xffff, P.noise + fr.noise_off, jac + fr.jac_off);
+      for (int c = 0; c < 3; ++c) {
+        H[6 * r + c] = -h.a[3 * c + r];  // (-h')(r, c)
+        H[6 * r + 3 + c] = (r == c) ? 1.0 : 0.0;
+      }
+  }
+}
+__global__ void __launch_bounds__(256) linearize_between_rot3_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                                     double* jac) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int f = list[i];
+  const FactorRec fr = P.frec[f];
+  double e[3], H[18];
+  between_rot3_eval<true>(P, f, fr, values, e, H);
+  store_linearized<3, 6>(e, H, fr, P, jac);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1134,239 +1298,19 @@ __global__ void __launch_bounds__(256) error_essential_kernel(DevProblem P, cons
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
-                      const double* values, double* jac, DevStatus* status, hipStream_t st, const SmartDev* smart) {
-  auto grid = [](int n) { return dim3((n + 255) / 256); };
-  // the generic family (priors, vector-space factors: few) rides in the first blocks of the first main family's launch
-  const int* glist = type_lists[3];
-  int gn = type_counts[3];
-  auto take = [&](int n) {  // blocks of a main launch: its own + the generic ones, handed out once
-    const int g = gn;
-    gn = 0;
-    return std::make_pair(dim3((n + 255) / 256 + (g + 255) / 256), g);
-  };
-  if (type_counts[0]) {
-    const auto gg = take(type_counts[0]);
-    linearize_sfm_kernel<<<gg.first, 256, 0, st>>>(P, type_lists[0], type_counts[0], values, jac, status, glist, gg.second);
-  }
-  if (type_counts[1]) {
-    const auto gg = take(type_counts[1]);
-    linearize_between_pose2_kernel<<<gg.first, 256, 0, st>>>(P, type_lists[1], type_counts[1], values, jac, glist, gg.second);
-  }
-  if (type_counts[2]) {
-    const auto gg = take(type_counts[2]);
-    linearize_between_pose3_kernel<<<gg.first, 256, 0, st>>>(P, type_lists[2], type_counts[2], values, jac, glist, gg.second);
-  }
-  if (gn) linearize_generic_kernel<<<grid(gn), 256, 0, st>>>(P, glist, gn, values, jac);
-  if (type_counts[4])
-    linearize_projection_kernel<false><<<grid(type_counts[4]), 256, 0, st>>>(P, type_lists[4], type_counts[4], values, jac,
-                                                                             status);
-  if (type_counts[5])
-    linearize_bearingrange_kernel<<<grid(type_counts[5]), 256, 0, st>>>(P, type_lists[5], type_counts[5], values, jac);
-  auto run = [&](auto kernel, int k) {
-    if (type_counts[k]) kernel<<<grid(type_counts[k]), 256, 0, st>>>(P, type_lists[k], type_counts[k], values, jac);
-  };
-  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_VECTOR, false>, TL_RANGE_POSE2_POINT);
-  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_POSE2, false>, TL_RANGE_POSE2_POSE);
-  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR, false>, TL_RANGE_POSE3_POINT);
-  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3, false>, TL_RANGE_POSE3_POSE);
-  run(linearize_bearing_kernel, TL_BEARING);
-  // the kernels that count their cheirality factors
-  auto run_s = [&](auto kernel, int k) {
-    if (type_counts[k]) kernel<<<grid(type_counts[k]), 256, 0, st>>>(P, type_lists[k], type_counts[k], values, jac, status);
-  };
-  run_s(linearize_stereo_kernel<false>, TL_STEREO);
-  // the forms with body_P_sensor, and GeneralSFMFactor2
-  run_s(linearize_projection_kernel<true>, TL_PROJECTION_SENSOR);
-  run_s(linearize_stereo_kernel<true>, TL_STEREO_SENSOR);
-  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_VECTOR, true>, TL_RANGE_POSE2_POINT_SENSOR);
-  run(linearize_range_kernel<GSX_VAR_POSE2, GSX_VAR_POSE2, true>, TL_RANGE_POSE2_POSE_SENSOR);
-  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_VECTOR, true>, TL_RANGE_POSE3_POINT_SENSOR);
-  run(linearize_range_kernel<GSX_VAR_POSE3, GSX_VAR_POSE3, true>, TL_RANGE_POSE3_POSE_SENSOR);
-  run_s(linearize_sfm2_kernel, TL_SFM2);
-  run(linearize_translation_kernel, TL_TRANSLATION);
-  run(linearize_bata_kernel, TL_BATA);
-  run(linearize_absolute_kernel, TL_ABSOLUTE);
-  run(linearize_between_rot3_kernel, TL_BETWEEN_ROT3);
-  run(linearize_gps_calib_kernel, TL_GPS_CALIB);
-  run(linearize_essential_kernel<TL_ESSENTIAL>, TL_ESSENTIAL);
-  run(linearize_essential_kernel<TL_ESSENTIAL_DEPTH>, TL_ESSENTIAL_DEPTH);
-  run(linearize_essential_kernel<TL_ESSENTIAL_DEPTH_ROTATED>, TL_ESSENTIAL_DEPTH_ROTATED);
-  run(linearize_essential_kernel<TL_ESSENTIAL_CALIB>, TL_ESSENTIAL_CALIB);
-  run(linearize_essential_kernel<TL_ESSENTIAL_CONSTRAINT>, TL_ESSENTIAL_CONSTRAINT);
-  run(linearize_essential_kernel<TL_PRIOR_UNIT3>, TL_PRIOR_UNIT3);
-  run(linearize_essential_kernel<TL_PRIOR_ESSENTIAL>, TL_PRIOR_ESSENTIAL);
-  if (type_counts[TL_SMART] && smart) {   // triangulate (cache consulted and updated), then marginalize the landmark
-    launch_smart_triangulate(P, type_lists[TL_SMART], type_counts[TL_SMART], values, *smart, st);
-    launch_smart_linearize(P, type_lists[TL_SMART], type_counts[TL_SMART], *smart, jac, st);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // graph error (NoiseModelFactor::error, gtsam/nonlinear/NonlinearFactor.cpp:138-149)
 // ---------------------------------------------------------------------------------------------
-// FT / FV >= 0: the factor type / the type of its first variable are known at compile time (the per-type kernels below:
-// the one-kernel-for-all form needed 247 registers, two waves a SIMD); -1: read from the record.
-// SENSOR: the form with body_P_sensor behind the measurement (projection, stereo, range: kernels of their own only).
-template <int FT = -1, int FV = -1, bool SENSOR = false>
+// TL_GENERIC (every other list: error_family_kernel and its kin above): priors through local_coords and BetweenFactor on
+// vector spaces, runtime dimensions
 __device__ inline double factor_error(const DevProblem& P, int f, const double* values) {
   const FactorRec fr = P.frec[f];
-  const int type = FT >= 0 ? FT : (fr.type_kind & 0xff);
-  if (type == GSX_F_LINEAR) return 0.0;
-  const int kind = (fr.type_kind >> 8) & 0xffff;
+  const int kind = (fr.type_kind >> 8) & 0xffff, m = fr.rows_dim & 0xff;
   const double* np = P.noise + fr.noise_off;
   const double* z = P.meas + fr.meas_off;
-  if (type == GSX_F_SFM) {
-    const double* cam = values + fr.s0;
-    const double* pt = values + fr.s1;
-    double camr[17], ptr3[3], pi[2], e[2];
-#pragma unroll
-    for (int k = 0; k < 17; ++k) camr[k] = cam[k];
-    ptr3[0] = pt[0]; ptr3[1] = pt[1]; ptr3[2] = pt[2];
-    if (!sfm_project(camr, ptr3, pi, nullptr, nullptr)) return 0.0;
-    e[0] = pi[0] - z[0];
-    e[1] = pi[1] - z[1];
-    return whitened_half_sqnorm<2>(e, kind, np);
-  }
-  if (type == GSX_F_BEARINGRANGE) {
-    const double* pose = values + fr.s0;
-    const double* pt = values + fr.s1;
-    double ps[3] = {pose[0], pose[1], pose[2]}, p2[2] = {pt[0], pt[1]}, br[2], e[2];
-    bearing_range_2d(ps, p2, br, nullptr, nullptr);
-    e[0] = wrap_angle(br[0] - z[0]);
-    e[1] = br[1] - z[1];
-    return whitened_half_sqnorm<2>(e, kind, np);
-  }
-  if (type == GSX_F_PROJECTION) {
-    const double* pose = values + fr.s0;
-    const double* pt = values + fr.s1;
-    double pr[12], p3[3], K[5], pi[2], e[2];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pr[k] = pose[k];
-    p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) K[k] = z[2 + k];
-    if constexpr (SENSOR) pose3_compose_sensor(pr, z + 7);
-    if (pinhole_project_s2(pr, p3, K, pi, nullptr, nullptr)) {
-      e[0] = pi[0] - z[0];
-      e[1] = pi[1] - z[1];
-    } else {
-      e[0] = e[1] = 2.0 * K[0];
-    }
-    return whitened_half_sqnorm<2>(e, kind, np);
-  }
-  // the families below have kernels of their own only (launch_error): compiled out of the <-1, -1> form
-  if constexpr (FT == GSX_F_RANGE && FV == GSX_VAR_POSE2) {
-    const double* a1 = values + fr.s0;
-    const double* a2 = values + fr.s1;  // a point, or a pose whose translation comes first
-    double ps[3] = {a1[0], a1[1], a1[2]}, p2[2] = {a2[0], a2[1]}, e[1];
-    if constexpr (SENSOR) e[0] = range_2d_cs(pose2_compose_sensor(ps, z + 1), p2, nullptr, nullptr) - z[0];
-    else e[0] = range_2d(ps, p2, nullptr, nullptr) - z[0];
-    return whitened_half_sqnorm<1>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_RANGE && FV == GSX_VAR_POSE3) {
-    const double* a1 = values + fr.s0;
-    const double* a2 = values + fr.s1 + ((fr.rows_dim >> 16) == 13 ? 9 : 0);  // 13 columns: the other is a pose (R9 t3)
-    double pr[12], p3[3] = {a2[0], a2[1], a2[2]}, e[1];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pr[k] = a1[k];
-    if constexpr (SENSOR) pose3_compose_sensor(pr, z + 1);
-    e[0] = range_3d(pr, p3, nullptr, nullptr) - z[0];
-    return whitened_half_sqnorm<1>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_BEARING) {
-    const double* pose = values + fr.s0;
-    const double* pt = values + fr.s1;
-    double ps[3] = {pose[0], pose[1], pose[2]}, p2[2] = {pt[0], pt[1]}, br[2], e[1];
-    bearing_range_2d(ps, p2, br, nullptr, nullptr);
-    e[0] = wrap_angle(br[0] - z[0]);
-    return whitened_half_sqnorm<1>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_STEREO) {
-    const double* pose = values + fr.s0;
-    const double* pt = values + fr.s1;
-    double pr[12], p3[3], K[6], pi[3], e[3];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pr[k] = pose[k];
-    p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) K[k] = z[3 + k];
-    if constexpr (SENSOR) pose3_compose_sensor(pr, z + 9);
-    if (stereo_project(pr, p3, K, pi, nullptr, nullptr)) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) e[r] = pi[r] - z[r];
-    } else {
-      e[0] = e[1] = e[2] = 2.0 * K[0];
-    }
-    return whitened_half_sqnorm<3>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_SFM2) {  // GeneralSFMFactor2: zero behind the camera (GeneralSFMFactor.h:270-277)
-    const double* pose = values + fr.s0;
-    const double* pt = values + fr.s1;
-    const double* cal = values + P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]];
-    double pr[12], p3[3], K[5], pi[2], e[2];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pr[k] = pose[k];
-    p3[0] = pt[0]; p3[1] = pt[1]; p3[2] = pt[2];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) K[k] = cal[k];
-    if (!pinhole_project_s2(pr, p3, K, pi, nullptr, nullptr)) return 0.0;
-    e[0] = pi[0] - z[0];
-    e[1] = pi[1] - z[1];
-    return whitened_half_sqnorm<2>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_TRANSLATION) {  // normalize(Tb - Ta) - z (gtsam/sfm/TranslationFactor.h:68-78)
-    const double* ta = values + fr.s0;
-    const double* tb = values + fr.s1;
-    const double x = tb[0] - ta[0], y = tb[1] - ta[1], w = tb[2] - ta[2], nrm = sqrt(x * x + y * y + w * w);
-    double e[3] = {x / nrm - z[0], y / nrm - z[1], w / nrm - z[2]};
-    return whitened_half_sqnorm<3>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_BILINEAR_TRANSLATION) {  // |s| (Tb - Ta) - z (:133-149)
-    const double* ta = values + fr.s0;
-    const double* tb = values + fr.s1;
-    const double a = fabs(values[P.var_state_off[P.f_vars[P.f_key_ptr[f] + 2]]]);
-    double e[3] = {(tb[0] - ta[0]) * a - z[0], (tb[1] - ta[1]) * a - z[1], (tb[2] - ta[2]) * a - z[2]};
-    return whitened_half_sqnorm<3>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_GPS) {  // GPSFactorArmCalib: t + R bL - nT, the lever arm the second key
-    const double* x = values + fr.s0;
-    const double* b = values + fr.s1;
-    double e[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) e[r] = (x[9 + r] + (x[3 * r] * b[0] + x[3 * r + 1] * b[1] + x[3 * r + 2] * b[2])) - z[r];
-    return whitened_half_sqnorm<3>(e, kind, np);
-  }
-  if constexpr (FT == GSX_F_BETWEEN && FV == GSX_VAR_ROT3) {  // Logmap(z' R1' R2)
-    M3 R1, R2, Z;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      R1.a[k] = values[fr.s0 + k];
-      R2.a[k] = values[fr.s1 + k];
-      Z.a[k] = z[k];
-    }
-    const V3 w = so3_logmap(mul(transpose(Z), mul(transpose(R1), R2)));
-    double e[3] = {w.x, w.y, w.z};
-    return whitened_half_sqnorm<3>(e, kind, np);
-  }
-  const int vt = FV >= 0 ? FV : ((fr.type_kind >> 24) & 0xff);
-  if (type == GSX_F_BETWEEN && vt == GSX_VAR_POSE2) {
-    const P2 h = compose(inverse(load_pose2(values + fr.s0)), load_pose2(values + fr.s1));
-    const P2 zh = compose(inverse(load_pose2(z)), h);
-    double e[3] = {zh.x, zh.y, theta(zh)};
-    return whitened_half_sqnorm<3>(e, kind, np);
-  }
-  if (type == GSX_F_BETWEEN && vt == GSX_VAR_POSE3) {
-    const P3 h = between(load_pose3(values + fr.s0), load_pose3(values + fr.s1));
-    double e[6];
-    pose3_logmap(compose(inverse(load_pose3(z)), h), e);
-    return whitened_half_sqnorm<6>(e, kind, np);
-  }
-  // generic: priors, vector between
-  const int m = fr.rows_dim & 0xff;
   double e[9];
-  if (type == GSX_F_PRIOR) {
-    local_coords(vt, (fr.rows_dim >> 8) & 0xff, values + fr.s0, z, e);
+  if ((fr.type_kind & 0xff) == GSX_F_PRIOR) {
+    local_coords((fr.type_kind >> 24) & 0xff, (fr.rows_dim >> 8) & 0xff, values + fr.s0, z, e);
   } else {
     const double* x1 = values + fr.s0;
     const double* x2 = values + fr.s1;
@@ -1388,6 +1332,14 @@ __device__ inline double factor_error(const DevProblem& P, int f, const double* 
   if (loss) return robust_loss(loss, np[noise_base_params(base, m)], sqrt(s));
   return 0.5 * s;
 }
+__global__ void __launch_bounds__(256) error_generic_kernel(DevProblem P, const int* list, int n, const double* values,
+                                                            double* partials) {
+  double acc = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    acc += factor_error(P, list[i], values);
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
 
 __global__ void __launch_bounds__(256) reduce_final_kernel(const double* partials, int n, int stride, double* scalars,
                                                            int slot) {
@@ -1406,88 +1358,123 @@ __global__ void __launch_bounds__(256) reduce_final_pair_kernel(const double* pa
   if (threadIdx.x == 0) scalars[slot0 + blockIdx.x] = s;
 }
 
-// the factors of one type list (the lists of launch_linearize), the type a compile-time constant
-template <int FT, int FV, bool SENSOR = false>
-__global__ void __launch_bounds__(256) error_list_kernel(DevProblem P, const int* list, int n, const double* values,
-                                                         double* partials) {
-  double acc = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    acc += factor_error<FT, FV, SENSOR>(P, list[i], values);
-  const double s = block_sum(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+// ---------------------------------------------------------------------------------------------
+// THE LIST TABLE: the linearize kernel and the error kernel of every factor list, in one place.  launch_linearize and
+// launch_error instantiate every list 0 .. kNumTypeLists - 1, so a TL_* without a line here does not compile.  TL_SMART
+// alone is not here: it has launch functions, not kernels (smart.hip), and both launchers name them.
+// ---------------------------------------------------------------------------------------------
+template <bool LIN, class L, class E>
+constexpr auto pick(L lin, E err) {
+  if constexpr (LIN) return lin;
+  else return err;
+}
+template <int TL, bool LIN>
+constexpr auto list_kernel() {
+  constexpr int POSE2 = GSX_VAR_POSE2, POSE3 = GSX_VAR_POSE3, VEC = GSX_VAR_VECTOR;
+  if constexpr (TL == TL_SFM) return pick<LIN>(linearize_sfm_kernel, error_family_kernel<2, sfm_residual>);
+  else if constexpr (TL == TL_BETWEEN_POSE2) return pick<LIN>(linearize_between_pose2_kernel, error_family_kernel<3, between_pose2_eval<false>>);
+  else if constexpr (TL == TL_BETWEEN_POSE3) return pick<LIN>(linearize_between_pose3_kernel, error_family_kernel<6, between_pose3_eval<false>>);
+  else if constexpr (TL == TL_GENERIC) return pick<LIN>(linearize_generic_kernel, error_generic_kernel);
+  else if constexpr (TL == TL_PROJECTION) return pick<LIN>(linearize_projection_kernel<false>, error_family_kernel<2, projection_residual<false>>);
+  else if constexpr (TL == TL_BEARINGRANGE) return pick<LIN>(linearize_bearing_range_kernel<2>, error_family_kernel<2, bearing_range_eval<2, false>>);
+  else if constexpr (TL == TL_RANGE_POSE2_POINT) return pick<LIN>(linearize_range_kernel<POSE2, VEC, false>, error_family_kernel<1, range_eval<POSE2, VEC, false, false>>);
+  else if constexpr (TL == TL_RANGE_POSE2_POSE) return pick<LIN>(linearize_range_kernel<POSE2, POSE2, false>, error_family_kernel<1, range_eval<POSE2, POSE2, false, false>>);
+  else if constexpr (TL == TL_RANGE_POSE3_POINT) return pick<LIN>(linearize_range_kernel<POSE3, VEC, false>, error_family_kernel<1, range_eval<POSE3, VEC, false, false>>);
+  else if constexpr (TL == TL_RANGE_POSE3_POSE) return pick<LIN>(linearize_range_kernel<POSE3, POSE3, false>, error_family_kernel<1, range_eval<POSE3, POSE3, false, false>>);
+  else if constexpr (TL == TL_BEARING) return pick<LIN>(linearize_bearing_range_kernel<1>, error_family_kernel<1, bearing_range_eval<1, false>>);
+  else if constexpr (TL == TL_STEREO) return pick<LIN>(linearize_stereo_kernel<false>, error_family_kernel<3, stereo_residual<false>>);
+  else if constexpr (TL == TL_PROJECTION_SENSOR) return pick<LIN>(linearize_projection_kernel<true>, error_family_kernel<2, projection_residual<true>>);
+  else if constexpr (TL == TL_STEREO_SENSOR) return pick<LIN>(linearize_stereo_kernel<true>, error_family_kernel<3, stereo_residual<true>>);
+  else if constexpr (TL == TL_RANGE_POSE2_POINT_SENSOR) return pick<LIN>(linearize_range_kernel<POSE2, VEC, true>, error_family_kernel<1, range_eval<POSE2, VEC, true, false>>);
+  else if constexpr (TL == TL_RANGE_POSE2_POSE_SENSOR) return pick<LIN>(linearize_range_kernel<POSE2, POSE2, true>, error_family_kernel<1, range_eval<POSE2, POSE2, true, false>>);
+  else if constexpr (TL == TL_RANGE_POSE3_POINT_SENSOR) return pick<LIN>(linearize_range_kernel<POSE3, VEC, true>, error_family_kernel<1, range_eval<POSE3, VEC, true, false>>);
+  else if constexpr (TL == TL_RANGE_POSE3_POSE_SENSOR) return pick<LIN>(linearize_range_kernel<POSE3, POSE3, true>, error_family_kernel<1, range_eval<POSE3, POSE3, true, false>>);
+  else if constexpr (TL == TL_SFM2) return pick<LIN>(linearize_sfm2_kernel, error_family_kernel<2, sfm2_residual>);
+  else if constexpr (TL == TL_TRANSLATION) return pick<LIN>(linearize_translation_kernel, error_family_kernel<3, translation_eval<false>>);
+  else if constexpr (TL == TL_BATA) return pick<LIN>(linearize_bata_kernel, error_family_kernel<3, bata_eval<false>>);
+  else if constexpr (TL == TL_ABSOLUTE) return pick<LIN>(linearize_absolute_kernel, error_absolute_kernel);
+  else if constexpr (TL == TL_BETWEEN_ROT3) return pick<LIN>(linearize_between_rot3_kernel, error_family_kernel<3, between_rot3_eval<false>>);
+  else if constexpr (TL == TL_GPS_CALIB) return pick<LIN>(linearize_gps_calib_kernel, error_family_kernel<3, gps_calib_eval<false>>);
+  else if constexpr (TL >= TL_ESSENTIAL && TL < kNumTypeLists) return pick<LIN>(linearize_essential_kernel<TL>, error_essential_kernel<TL>);
+  else static_assert(TL < 0, "a TL_* without its kernels in the list table");
+}
+template <class F, int... TL>
+static void for_each_list(F&& f, std::integer_sequence<int, TL...>) {
+  (f(std::integral_constant<int, TL>{}), ...);
 }
 
+// the linearize launch of list TL.  The generic family (priors, vector-space factors: few) rides in the first blocks of the
+// first non-empty main family's launch: `gn` is what of it is still to be taken, a launch of its own only if none did
+template <int TL>
+static void launch_list_linearize(const DevProblem& P, const int* const lists[kNumTypeLists], const int counts[kNumTypeLists],
+                                  const double* values, double* jac, DevStatus* status, hipStream_t st, int& gn) {
+  static_assert(TL_SFM < TL_GENERIC && TL_BETWEEN_POSE2 < TL_GENERIC && TL_BETWEEN_POSE3 < TL_GENERIC, "hosts come first");
+  const int n = counts[TL];
+  [[maybe_unused]] const dim3 grid((n + 255) / 256);
+  if constexpr (TL == TL_SMART) {
+    // (launch_linearize: after every other list)
+  } else if constexpr (TL == TL_GENERIC) {
+    if (gn) linearize_generic_kernel<<<dim3((gn + 255) / 256), 256, 0, st>>>(P, lists[TL], gn, values, jac);
+  } else if (n) {
+    constexpr auto kernel = list_kernel<TL, true>();
+    if constexpr (TL == TL_SFM || TL == TL_BETWEEN_POSE2 || TL == TL_BETWEEN_POSE3) {
+      const int g = gn;  // blocks of a main launch: its own + the generic ones, handed out once
+      gn = 0;
+      const dim3 both((n + 255) / 256 + (g + 255) / 256);
+      if constexpr (TL == TL_SFM) kernel<<<both, 256, 0, st>>>(P, lists[TL], n, values, jac, status, lists[TL_GENERIC], g);
+      else kernel<<<both, 256, 0, st>>>(P, lists[TL], n, values, jac, lists[TL_GENERIC], g);
+    } else if constexpr (TL == TL_PROJECTION || TL == TL_STEREO || TL == TL_PROJECTION_SENSOR || TL == TL_STEREO_SENSOR ||
+                         TL == TL_SFM2) {
+      kernel<<<grid, 256, 0, st>>>(P, lists[TL], n, values, jac, status);  // the kernels that count their cheirality factors
+    } else {
+      kernel<<<grid, 256, 0, st>>>(P, lists[TL], n, values, jac);
+    }
+  }
+}
+void launch_linearize(const DevProblem& P, const int* const type_lists[kNumTypeLists], const int type_counts[kNumTypeLists],
+                      const double* values, double* jac, DevStatus* status, hipStream_t st, const SmartDev* smart) {
+  int gn = type_counts[TL_GENERIC];
+  for_each_list([&](auto tl) { launch_list_linearize<decltype(tl)::value>(P, type_lists, type_counts, values, jac, status, st, gn); },
+                std::make_integer_sequence<int, kNumTypeLists>{});
+  if (type_counts[TL_SMART] && smart) {   // triangulate (cache consulted and updated), then marginalize the landmark
+    launch_smart_triangulate(P, type_lists[TL_SMART], type_counts[TL_SMART], values, *smart, st);
+    launch_smart_linearize(P, type_lists[TL_SMART], type_counts[TL_SMART], *smart, jac, st);
+  }
+}
+
+// the error launch of list TL: nb blocks, a partial sum each
+template <int TL>
+static void launch_list_error(const DevProblem& P, const int* list, int n, const double* values, double* out, int nb,
+                              hipStream_t st, const SmartDev* smart) {
+  if constexpr (TL == TL_SMART) {  // triangulate at `values` (cache consulted and updated), then the reprojection errors
+    launch_smart_triangulate(P, list, n, values, *smart, st);
+    launch_smart_error(P, list, n, *smart, out, nb, st);
+  } else {
+    list_kernel<TL, false>()<<<nb, 256, 0, st>>>(P, list, n, values, out);
+  }
+}
 void launch_error(const DevProblem& P, const int* const type_lists[kNumTypeLists],
                   const int type_counts[kNumTypeLists], const double* values, double* partials, int cap, double* scalars,
                   int slot, hipStream_t st, const SmartDev* smart) {
   // a launch per non-empty list, its blocks a share of the partial sums proportional to its factors; the sums are added in
-  // list order, block order: deterministic
+  // list order, block order: deterministic.  held_slots (kernels.h): slots held back so that a list of few factors still
+  // gets its block
   long long total = 0;
   for (int k = 0; k < kNumTypeLists; ++k) total += type_counts[k];
-  // slots held back so that a list of few factors still gets its block: one per list a graph can fill.  A graph without
-  // the sensor forms and GSX_F_SFM2 keeps the shares — hence the summation order, hence the bits — it had before they came
-  bool new_lists = false;
-  for (int k = TL_PROJECTION_SENSOR; k < TL_SMART; ++k) new_lists = new_lists || type_counts[k] > 0;
-  // (likewise a graph without smart factors keeps the shares it had before TL_SMART came, and one without the translation
-  // factors those it had before TL_TRANSLATION and TL_BATA came)
-  // (and one without the absolute-measurement lists those it had before they came)
-  // (and one without the epipolar lists those it had before they came)
-  int n_essential = 0;
-  for (int k = TL_ESSENTIAL; k < kNumTypeLists; ++k) n_essential += type_counts[k];
-  const int held = n_essential > 0
-                       ? kNumTypeLists
-                   : type_counts[TL_ABSOLUTE] + type_counts[TL_BETWEEN_ROT3] + type_counts[TL_GPS_CALIB] > 0
-                       ? TL_ESSENTIAL
-                   : type_counts[TL_TRANSLATION] + type_counts[TL_BATA] > 0
-                       ? TL_ABSOLUTE
-                       : (type_counts[TL_SMART] > 0 ? TL_TRANSLATION : (new_lists ? TL_SMART : TL_PROJECTION_SENSOR));
+  const int held = held_slots(type_counts);
   int off = 0;
-  for (int k = 0; k < kNumTypeLists; ++k) {
-    const int n = type_counts[k];
-    if (!n) continue;
-    int nb = (n + 255) / 256;
-    const int share = (int)std::max<long long>(1, (long long)(cap - held) * n / std::max<long long>(total, 1));
-    nb = std::min(nb, share);
-    double* out = partials + off;
-    switch (k) {
-      case 0: error_list_kernel<GSX_F_SFM, GSX_VAR_CAMERA><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case 1: error_list_kernel<GSX_F_BETWEEN, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case 2: error_list_kernel<GSX_F_BETWEEN, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case 4: error_list_kernel<GSX_F_PROJECTION, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case 5: error_list_kernel<GSX_F_BEARINGRANGE, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_RANGE_POSE2_POINT:
-      case TL_RANGE_POSE2_POSE: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_RANGE_POSE3_POINT:
-      case TL_RANGE_POSE3_POSE: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_BEARING: error_list_kernel<GSX_F_BEARING, GSX_VAR_POSE2><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_STEREO: error_list_kernel<GSX_F_STEREO, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_PROJECTION_SENSOR: error_list_kernel<GSX_F_PROJECTION, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_STEREO_SENSOR: error_list_kernel<GSX_F_STEREO, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_RANGE_POSE2_POINT_SENSOR:
-      case TL_RANGE_POSE2_POSE_SENSOR: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE2, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_RANGE_POSE3_POINT_SENSOR:
-      case TL_RANGE_POSE3_POSE_SENSOR: error_list_kernel<GSX_F_RANGE, GSX_VAR_POSE3, true><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_SFM2: error_list_kernel<GSX_F_SFM2, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_TRANSLATION: error_list_kernel<GSX_F_TRANSLATION, GSX_VAR_VECTOR><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_BATA: error_list_kernel<GSX_F_BILINEAR_TRANSLATION, GSX_VAR_VECTOR><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_ABSOLUTE: error_absolute_kernel<<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_BETWEEN_ROT3: error_list_kernel<GSX_F_BETWEEN, GSX_VAR_ROT3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_GPS_CALIB: error_list_kernel<GSX_F_GPS, GSX_VAR_POSE3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_ESSENTIAL: error_essential_kernel<TL_ESSENTIAL><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_ESSENTIAL_DEPTH: error_essential_kernel<TL_ESSENTIAL_DEPTH><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_ESSENTIAL_DEPTH_ROTATED: error_essential_kernel<TL_ESSENTIAL_DEPTH_ROTATED><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_ESSENTIAL_CALIB: error_essential_kernel<TL_ESSENTIAL_CALIB><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_ESSENTIAL_CONSTRAINT: error_essential_kernel<TL_ESSENTIAL_CONSTRAINT><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_PRIOR_UNIT3: error_essential_kernel<TL_PRIOR_UNIT3><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_PRIOR_ESSENTIAL: error_essential_kernel<TL_PRIOR_ESSENTIAL><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-      case TL_SMART:   // triangulate at `values` (cache consulted and updated), then the reprojection errors
-        launch_smart_triangulate(P, type_lists[k], n, values, *smart, st);
-        launch_smart_error(P, type_lists[k], n, *smart, out, nb, st);
-        break;
-      default: error_list_kernel<-1, -1><<<nb, 256, 0, st>>>(P, type_lists[k], n, values, out); break;
-    }
-    off += nb;
-  }
+  for_each_list(
+      [&](auto tl) {
+        constexpr int k = decltype(tl)::value;
+        const int n = type_counts[k];
+        if (!n) return;
+        int nb = (n + 255) / 256;
+        const int share = (int)std::max<long long>(1, (long long)(cap - held) * n / std::max<long long>(total, 1));
+        nb = std::min(nb, share);
+        launch_list_error<k>(P, type_lists[k], n, values, partials + off, nb, st, smart);
+        off += nb;
+      },
+      std::make_integer_sequence<int, kNumTypeLists>{});
   reduce_final_kernel<<<1, 256, 0, st>>>(partials, off, 1, scalars, slot);
 }
 

@@ -1,4 +1,4 @@
-"""Every linearize_* kernel, the error_list_kernel family and retract_kernel at the edges of their branches, against the
+"""Every linearize_* kernel, the error kernels and retract_kernel at the edges of their branches, against the
 50-digit restatement of tests/_mp_restatement.py (pinned by tests/test_host_restatement.py; NOT a twin of
 csrc/device_geometry.h as oracle/geometry.h is).  A sweep packs its cases into ONE graph, factor i = case i, several hundred
 factors and never a multiple of 256: one handle and one gsx_linearize judge all of it, across block boundaries.
