@@ -215,9 +215,13 @@ struct Context {
   // that kernel).  GSX_FUSED_STAR=0 at gsx_create: the two-step path (star assembly, then front_leaf).
   bool fused_star_env = true;    // (read once per handle)
   bool fused_star = false;       // this tree has star leaves and the handle eliminates them fused
+  // Several star leaves share a wave (kernels.h: star_leaf_pack_class): the star records of a launch group are a stable
+  // partition into the cliques of 16 lanes, of 32 lanes and of a wave.  GSX_STAR_LEAF_PACK=0 at gsx_create: a wave each.
+  bool star_leaf_pack_env = true;   // (read once per handle)
   struct LeafSplit {
     int sbegin, scount;          // the launch group's star leaves: range of d_star_recs
     int rbegin, rcount;          // its other leaves: range of d_leaf_rest_recs
+    int s16, s32;                // of scount, the leading cliques of 16 lanes and the next of 32 (the others: a wave)
   };
   std::vector<LeafSplit> leaf_split;   // per launch group of leaf_launch[0] (fused_star only)
   DevBuf<StarLeafRec> d_star_recs;

@@ -53,7 +53,9 @@ struct LeafRec {
   int dA, rows, loc, toff;
   int fvar_ptr, front, pad0, pad1;
 };
-// The three classes of a leaf back-substitution launch (backsolve_leaf_kernel): cliques and workgroups of each
+// The three classes of a leaf launch that puts several cliques in a wave (backsolve_leaf_kernel; front_star_leaf_packed_kernel,
+// with n64 = 0):
+// cliques and workgroups of each
 struct LeafPack {
   int n16, n32, n64, nb16, nb32;
 };
@@ -67,6 +69,9 @@ static_assert(16 * kLeafPackRows <= 64 && 32 * kLeafPackRows <= 128, "classes of
 // the variable's term records (three per factor: own block, partner block, rhs — the first factor's give the shape), 2-row
 // factors at even offsets only; the clique's rows are the panel's (n = panel rows, own rows first, hmap a permutation).
 constexpr int kStarMaxD = 3;
+// Passes over its partner rows that a clique sharing a wave may take (star_leaf_pack_class): the wave runs to the passes
+// of its tallest group, so the bound is the most a short clique waits for a neighbour.  Reasoned, not measured.
+constexpr int kStarPackPasses = 4;
 // The record also carries what cuts the dependent loads of a clique to record -> data: the factors' [A b] offsets when
 // they are evenly spaced (jstride > 0: factor q at jac0 + q jstride — the observations of a landmark stored together; else
 // through the term records) and the clique row of every partner row (prow: a row map per clique, in factor order).
@@ -361,10 +366,13 @@ void launch_front_leaf(const DevProblem& P, const DevSymbolic& S, const LeafRec*
                        const double* H, const double* damp, const double* scalars, double* arena, DevStatus* status,
                        hipStream_t st);
 // the star leaves of one launch group (front_star_leaf_kernel): H assembly and front_leaf of those cliques in one pass, same
-// bits; the rhs rows of their H panels are written, the rest of those panels is not
-void launch_front_star_leaf(const DevSymbolic& S, const StarLeafRec* recs, int count, const int* prow, const double* jac,
-                            const double* damp, const double* scalars, double* H, double* arena, DevStatus* status,
-                            hipStream_t st);
+// bits; the rhs rows of their H panels are written, the rest of those panels is not.  recs: the n16 cliques that take 16
+// lanes of a wave, then the n32 that take 32, then n64 eliminated a wave each.  star_leaf_pack_class: the lanes a clique of
+// nf factors with partners of dimension dB gets (16, 32 or 64).
+void launch_front_star_leaf(const DevSymbolic& S, const StarLeafRec* recs, int n16, int n32, int n64, const int* prow,
+                            const double* jac, const double* damp, const double* scalars, double* H, double* arena,
+                            DevStatus* status, hipStream_t st);
+int star_leaf_pack_class(int nf, int dB);
 // Deterministic extend-add into big parents (big_gather).
 // A source is either a block of a child's stored Schur complement (F = 0: entry (i, j) at off + i + j ld) or, for a
 // lean leaf child, the product form -W_b W_a' with W_b = rows off.., W_a = rows off + d2.. of the child's n x F L panel.

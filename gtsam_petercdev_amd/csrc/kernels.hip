@@ -2034,7 +2034,10 @@ __global__ void __launch_bounds__(256) assemble_h_diag_kernel(DevProblem P, DevS
 // The entries of a star variable's panel, shared by the star assembly below and by front_star_leaf_kernel (which forms
 // them in registers instead of storing them): both must produce the same bits.  Column ci of a factor's [A b] against
 // column cj; a 2-row factor at an even offset loads each column as one 16-byte pair.
-__device__ __forceinline__ double star_pair_dot(double2 x, double2 y) { return x.x * y.x + x.y * y.y; }
+// The rounding is spelled out — the second product rounded, the first fused into the sum, which is what the compiler
+// made of x.x * y.x + x.y * y.y in the assembly kernels — because its contraction is free to fuse either product: written
+// as the plain sum, front_star_leaf_group<16> and <32> differed from <64> in the last bit of some entries.
+__device__ __forceinline__ double star_pair_dot(double2 x, double2 y) { return fma(x.x, y.x, x.y * y.y); }
 // a partner-block entry: one factor's product
 __device__ __forceinline__ double star_entry(const double* Jf, int m, bool pair, int ci, int cj) {
   if (pair) return star_pair_dot(reinterpret_cast<const double2*>(Jf)[ci], reinterpret_cast<const double2*>(Jf)[cj]);
@@ -3511,14 +3514,27 @@ __device__ __forceinline__ double readlane_f64_via_i64(double v, int src_lane) {
 // operation's rounding (fsub(fma(a, b, c * d), e * f) -> fma(a, b, fma(c, d, -e * f))) across what is a store in the
 // two-step path.  It emits no instruction.
 __device__ __forceinline__ void as_stored(double& v) { asm volatile("" : "+v"(v)); }
-__global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, const StarLeafRec* recs, int count,
-                                                              const int* prow, const double* jac, const double* damp,
-                                                              const double* scalars, double* H, double* arena,
-                                                              DevStatus* status) {
+// SEVERAL cliques to a wave (GL = 16 or 32 lanes a clique: the host's rule is star_leaf_pack_class), or the wave form
+// (GL = 64).  A group is the wave form on its own lanes: lane lp of the group stands where lane lp of the wave stood, the
+// passes step by GL, and a factor's products are read from the group's lane base + q — a shuffle, since base differs from
+// group to group, where the wave form reads a lane.  nf, d and dB are the group's own: the loops below run to each lane's
+// bounds, so the wave runs to the largest of its groups while a group adds a term only below ITS nf.  Entry for entry
+// the operations and their order are the wave form's: same bits.  A group past `count` leaves; no other group reads it.
+template <int GL>
+__device__ __forceinline__ void front_star_leaf_group(const DevSymbolic& S, const StarLeafRec* recs, int count, int k0,
+                                                      const int* prow, const double* jac, const double* damp,
+                                                      const double* scalars, double* H, double* arena,
+                                                      DevStatus* status) {
+  static_assert(GL == 16 || GL == 32 || GL == 64, "lanes a clique");
   constexpr int D = kStarMaxD;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63, lp = lane & (GL - 1), base = lane - lp;
+  const int w = GL == 64 ? __builtin_amdgcn_readfirstlane(k0) : k0 + lane / GL;
   if (w >= count) return;
+  // factor q's products, from the lane that holds them
+  auto from_factor = [&](double v, int q) {
+    if constexpr (GL == 64) return readlane_f64_via_i64(v, q);
+    else return shfl_f64(v, base + q);
+  };
   const StarLeafRec rec = recs[w];
   const int n = rec.n, nf = rec.nf, d = rec.d, dB = rec.dB;
   const int colA = rec.colA, colB = rec.colB, colR = rec.colR;
@@ -3550,8 +3566,8 @@ __global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, con
   };
   double2 fa[D], fr, xb, ya[D];
   int R = 0;
-  load_factor(lane, fa, fr);
-  load_row(lane, R, xb, ya);
+  load_factor(lp, fa, fr);
+  load_row(lp, R, xb, ya);
   const double lambda = scalars[SC_LAMBDA];
   // ---- own block (lower triangle) and rhs row: sums over the factors in list order
   double O[D][D], G[D];
@@ -3561,9 +3577,9 @@ __global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, con
 #pragma unroll
     for (int c = 0; c < D; ++c) O[r][c] = 0.0;
   }
-  for (int fb = 0; fb < nf; fb += 64) {
-    if (fb > 0) load_factor(fb + lane, fa, fr);
-    const int nfb = min(64, nf - fb);
+  for (int fb = 0; fb < nf; fb += GL) {
+    if (fb > 0) load_factor(fb + lp, fa, fr);
+    const int nfb = min(GL, nf - fb);
     double po[D][D], pg[D];
 #pragma unroll
     for (int r = 0; r < D; ++r) {
@@ -3575,9 +3591,9 @@ __global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, con
 #pragma unroll
       for (int r = 0; r < D; ++r) {
         if (r >= d) break;
-        G[r] += readlane_f64_via_i64(pg[r], q);
+        G[r] += from_factor(pg[r], q);
 #pragma unroll
-        for (int c = 0; c <= r; ++c) O[r][c] += readlane_f64_via_i64(po[r][c], q);
+        for (int c = 0; c <= r; ++c) O[r][c] += from_factor(po[r][c], q);
       }
     }
   }
@@ -3634,8 +3650,8 @@ __global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, con
   };
   double* A = arena + rec.off;
   // ---- partner rows
-  for (int p0 = 0; p0 < npart; p0 += 64) {
-    if (p0 > 0) load_row(p0 + lane, R, xb, ya);
+  for (int p0 = 0; p0 < npart; p0 += GL) {
+    if (p0 > 0) load_row(p0 + lp, R, xb, ya);
     double x[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) {
@@ -3643,21 +3659,21 @@ __global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, con
       as_stored(x[j]);
     }
     eliminate(x);
-    if (p0 + lane < npart) {
+    if (p0 + lp < npart) {
 #pragma unroll
       for (int c = 0; c < D; ++c)
         if (c < d) A[R + (i64)c * n] = x[c];
     }
   }
   // ---- the own rows of L (clique rows 0..d-1) and the rhs row
-  if (lane < d) {
+  if (lp < d) {
 #pragma unroll
     for (int r = 0; r < D; ++r)
-      if (lane == r) {
+      if (lp == r) {
 #pragma unroll
         for (int c = 0; c <= r; ++c) A[r + (i64)c * n] = L[r][c];
       }
-  } else if (lane == d) {
+  } else if (lp == d) {
     double x[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) {
@@ -3672,13 +3688,49 @@ __global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, con
       if (c < d) A[Rg + (i64)c * n] = x[c];
   }
   // (choleskyPartial's conditioning test runs per reference clique after the factorization: cond_check_kernel)
-  if (fail && lane == 0) report_failure(status, rec.front);
+  if (fail && lp == 0) report_failure(status, rec.front);
 }
-void launch_front_star_leaf(const DevSymbolic& S, const StarLeafRec* recs, int count, const int* prow, const double* jac,
-                            const double* damp, const double* scalars, double* H, double* arena, DevStatus* status,
-                            hipStream_t st) {
-  if (count)
-    front_star_leaf_kernel<<<(count + 3) / 4, 256, 0, st>>>(S, recs, count, prow, jac, damp, scalars, H, arena, status);
+// The wave form, and the shared waves in a kernel of their own: a shared wave keeps its record and its row addresses per
+// lane, 124 vector registers against the wave form's 72 (4 waves a SIMD against 7), which one kernel of both forms would
+// put on the wave form too.
+__global__ void __launch_bounds__(256) front_star_leaf_kernel(DevSymbolic S, const StarLeafRec* recs, int count,
+                                                              const int* prow, const double* jac, const double* damp,
+                                                              const double* scalars, double* H, double* arena,
+                                                              DevStatus* status) {
+  front_star_leaf_group<64>(S, recs, count, blockIdx.x * 4 + (threadIdx.x >> 6), prow, jac, damp, scalars, H, arena, status);
+}
+// the workgroups of the 16-lane class first, then those of the 32-lane class (four waves a workgroup in each; recs is
+// partitioned the same way, kernels.h: LeafPack with n64 = 0)
+__global__ void __launch_bounds__(256) front_star_leaf_packed_kernel(DevSymbolic S, const StarLeafRec* recs, LeafPack pk,
+                                                                     const int* prow, const double* jac,
+                                                                     const double* damp, const double* scalars, double* H,
+                                                                     double* arena, DevStatus* status) {
+  const int wave = threadIdx.x >> 6;
+  const int b = blockIdx.x;
+  if (b < pk.nb16)
+    front_star_leaf_group<16>(S, recs, pk.n16, (b * 4 + wave) * 4, prow, jac, damp, scalars, H, arena, status);
+  else
+    front_star_leaf_group<32>(S, recs + pk.n16, pk.n32, ((b - pk.nb16) * 4 + wave) * 2, prow, jac, damp, scalars, H, arena,
+                              status);
+}
+// A clique takes the narrowest group that holds a factor a lane (nf <= G) and its partner rows in at most
+// kStarPackPasses passes of G; else the wave.  (The passes of a wave are those of its tallest group.)
+int star_leaf_pack_class(int nf, int dB) {
+  const int npart = nf * dB;
+  if (nf <= 16 && npart <= 16 * kStarPackPasses) return 16;
+  if (nf <= 32 && npart <= 32 * kStarPackPasses) return 32;
+  return 64;
+}
+
+void launch_front_star_leaf(const DevSymbolic& S, const StarLeafRec* recs, int n16, int n32, int n64, const int* prow,
+                            const double* jac, const double* damp, const double* scalars, double* H, double* arena,
+                            DevStatus* status, hipStream_t st) {
+  const LeafPack pk{n16, n32, 0, (n16 + 15) / 16, (n32 + 7) / 8};
+  if (n16 + n32)
+    front_star_leaf_packed_kernel<<<pk.nb16 + pk.nb32, 256, 0, st>>>(S, recs, pk, prow, jac, damp, scalars, H, arena, status);
+  if (n64)
+    front_star_leaf_kernel<<<(n64 + 3) / 4, 256, 0, st>>>(S, recs + n16 + n32, n64, prow, jac, damp, scalars, H, arena,
+                                                           status);
 }
 
 // ---------------------------------------------------------------------------------------------

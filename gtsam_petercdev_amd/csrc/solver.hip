@@ -206,8 +206,9 @@ static void dev_leaf_group(gsx_context* c, size_t g, hipStream_t st) {
   const SmallLaunch& sl = c->leaf_launch[0][g];
   if (c->fused_star && c->leaf_split[g].scount) {
     const gsx_context::LeafSplit& ls = c->leaf_split[g];
-    launch_front_star_leaf(c->DS, c->d_star_recs.p + ls.sbegin, ls.scount, c->d_star_prow.p, c->d_jac.p, c->d_damp.p,
-                           c->d_scalars.p, c->d_H.p, c->d_arena.p, c->d_status.p, st);
+    launch_front_star_leaf(c->DS, c->d_star_recs.p + ls.sbegin, ls.s16, ls.s32, ls.scount - ls.s16 - ls.s32,
+                           c->d_star_prow.p, c->d_jac.p, c->d_damp.p, c->d_scalars.p, c->d_H.p, c->d_arena.p,
+                           c->d_status.p, st);
     if (ls.rcount)
       launch_front_leaf(c->DP, c->DS, c->d_leaf_rest_recs.p + ls.rbegin, ls.rcount, sl.max_panel, sl.threads, c->d_H.p,
                         c->d_damp.p, c->d_scalars.p, c->d_arena.p, c->d_status.p, st);
@@ -484,6 +485,11 @@ gsx_status readback(gsx_context* c) {
 }
 
 bool factorization_ok(const gsx_context* c) { return c->h_status->n_fail == 0 && c->h_status->n_nonfinite == 0; }
+}  // namespace gsx
+// (for tests/test_gpu_star_leaf_packed.py; not part of the C ABI of include/gsx.h.)  The fronts that reported a failed
+// pivot in the factorization last read back (DevStatus::n_fail), -1 without a device.
+extern "C" int gsxtest_last_fail_count(gsx_context* c) { return c && c->has_device && c->h_status ? c->h_status->n_fail : -1; }
+namespace gsx {
 
 static uint64_t failing_key(gsx_context* c) {
   const DevStatus& s = *c->h_status;
@@ -663,6 +669,8 @@ gsx_status gsx_create(const gsx_problem_desc* desc, int32_t device, gsx_handle* 
     c->fused_star_env = !(e && std::atoi(e) == 0);
     e = std::getenv("GSX_BS_LEAF_PACK");
     c->bs_leaf_pack_env = !(e && std::atoi(e) == 0);
+    e = std::getenv("GSX_STAR_LEAF_PACK");
+    c->star_leaf_pack_env = !(e && std::atoi(e) == 0);
   }
   int n = 0;
   if (hipGetDeviceCount(&n) == hipSuccess && n > 0 && device >= 0 && device < n && hipSetDevice(device) == hipSuccess &&

@@ -345,6 +345,46 @@ extern "C" int gsxtest_backsolve_plan(gsx_context* c, int which, int* out, int c
   return (int)recs.size();
 }
 
+// The star records of one launch group as front_star_leaf_kernel takes them: a stable partition by the lanes a clique gets
+// (kernels.h: star_leaf_pack_class; !pack: every clique a wave, the table stays as it is).  n16, n32: the leading classes.
+// The arena rows of different cliques are disjoint, so their order changes no result.
+static void partition_star_leaves(StarLeafRec* recs, int count, bool pack, int& n16, int& n32) {
+  n16 = n32 = 0;
+  if (!pack) return;
+  auto lanes = [](const StarLeafRec& r) { return star_leaf_pack_class(r.nf, r.dB); };
+  StarLeafRec* m = std::stable_partition(recs, recs + count, [&](const StarLeafRec& r) { return lanes(r) == 16; });
+  StarLeafRec* e = std::stable_partition(m, recs + count, [&](const StarLeafRec& r) { return lanes(r) == 32; });
+  n16 = (int)(m - recs);
+  n32 = (int)(e - m);
+}
+
+// (for tests/test_host_star_leaf_partition.py, host only; not part of the C ABI of include/gsx.h.)  The partition above of
+// `count` records of nf[i] factors and partners of dimension dB[i]: order[k] = the index i of the record at place k,
+// counts = the cliques of 16 lanes, of 32 lanes and of a wave.
+extern "C" void gsxtest_star_leaf_partition(const int* nf, const int* dB, int count, int pack, int* order, int* counts) {
+  std::vector<StarLeafRec> recs((size_t)count);
+  for (int i = 0; i < count; ++i) {
+    recs[i] = StarLeafRec{};
+    recs[i].nf = nf[i];
+    recs[i].dB = dB[i];
+    recs[i].front = i;
+  }
+  partition_star_leaves(recs.data(), count, pack != 0, counts[0], counts[1]);
+  counts[2] = count - counts[0] - counts[1];
+  for (int k = 0; k < count; ++k) order[k] = recs[k].front;
+}
+// (for tests/test_gpu_star_leaf_packed.py.)  Per launch group of the leaf-kernel cliques a record (cliques of 16 lanes, of
+// 32 lanes, of a wave, leaves that are no star leaves); returns the number of groups — 0 when the handle does not fuse.
+extern "C" int gsxtest_star_leaf_classes(gsx_context* c, int* out, int cap) {
+  if (!c || !c->fused_star) return 0;
+  for (size_t g = 0; out && g < c->leaf_split.size() && (int)g < cap; ++g) {
+    const gsx_context::LeafSplit& ls = c->leaf_split[g];
+    const int r[4] = {ls.s16, ls.s32, ls.scount - ls.s16 - ls.s32, ls.rcount};
+    std::copy(r, r + 4, out + 4 * g);
+  }
+  return (int)c->leaf_split.size();
+}
+
 // ---- H assembly groups: variables bucketed by panel size (LDS) and term count (host only: gsx_get_hessian_groups
 //      reads the plan, and makes it itself on a handle without a device) ----
 void plan_hessian_groups(gsx_context* c) {
@@ -943,7 +983,7 @@ gsx_status upload_symbolic(gsx_context* c) {
       std::vector<int> prow;
       std::vector<LeafRec> rrec;
       for (const SmallLaunch& sl : c->leaf_launch[0]) {
-        gsx_context::LeafSplit ls{(int)srec.size(), 0, (int)rrec.size(), 0};
+        gsx_context::LeafSplit ls{(int)srec.size(), 0, (int)rrec.size(), 0, 0, 0};
         for (int k = sl.begin; k < sl.begin + sl.count; ++k) {
           const LeafRec& r = c->h_leaf_recs[k - c->leaf_base];
           if (!star_leaf(r)) {
@@ -966,6 +1006,7 @@ gsx_status upload_symbolic(gsx_context* c) {
                                      hm[r.n - 1], 0});
         }
         ls.scount = (int)srec.size() - ls.sbegin;
+        partition_star_leaves(srec.data() + ls.sbegin, ls.scount, c->star_leaf_pack_env, ls.s16, ls.s32);
         ls.rcount = (int)rrec.size() - ls.rbegin;
         c->leaf_split.push_back(ls);
       }

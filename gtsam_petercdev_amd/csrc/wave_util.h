@@ -31,6 +31,9 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane) {  // src
 __device__ __forceinline__ i64 shfl_i64(i64 v, int lane) {
   return ((i64)__shfl((int)(v >> 32), lane) << 32) | (unsigned)__shfl((int)(v & 0xffffffff), lane);
 }
+__device__ __forceinline__ double shfl_f64(double v, int lane) {
+  return __longlong_as_double(shfl_i64(__double_as_longlong(v), lane));
+}
 
 // 1 / sqrt(d) to full precision from the hardware seed (one cubic correction step)
 __device__ __forceinline__ double rsqrt_refined(double d) {
