@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(CSRC, "libgsx.so")
-SOURCES = ["problem.cpp", "ordering.cpp", "nd.cpp", "symbolic.cpp", "io.cpp", "lm_policy.cpp", "init_graph.cpp", "lago_graph.cpp", "translation_graph.cpp", "kernels.hip", "bigfront.hip", "constraint.hip", "marginals.hip", "pcg.hip", "initialize.hip", "lago.hip", "triangulate.hip", "smart.hip", "mfas.hip", "upload.hip", "solver.hip", "optimizers.hip", "incremental.hip"]
+SOURCES = ["problem.cpp", "ordering.cpp", "nd.cpp", "symbolic.cpp", "io.cpp", "lm_policy.cpp", "schedule_options.cpp", "init_graph.cpp", "lago_graph.cpp", "translation_graph.cpp", "kernels.hip", "bigfront.hip", "constraint.hip", "marginals.hip", "pcg.hip", "initialize.hip", "lago.hip", "triangulate.hip", "smart.hip", "mfas.hip", "upload.hip", "solver.hip", "optimizers.hip", "incremental.hip"]
 HEADERS = ["gsx_internal.h", "handle.h", "kernels.h", "device_geometry.h", "unit3_math.h", "init_math.h", "init_device.h", "triangulate_math.h", "smart_math.h", "wave_util.h", os.path.join("..", "..", "include", "gsx.h")]
 
 

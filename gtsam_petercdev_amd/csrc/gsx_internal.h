@@ -35,6 +35,44 @@ constexpr int kMedMaxPanel = 18432; // doubles of LDS for the panel: 144 KB
 constexpr int kMedMaxLeafKids = 8;  // a front with more childless small children than this stays blocked: its leaves are
                                     // LEAN only under a blocked parent (every BAL camera front: hundreds of landmarks)
 
+// The schedule switches of one handle: which kernels and what launch geometry its plans choose.  gsx_create reads them from
+// the environment once (schedule_options_from_env: the only reader) and the handle keeps them — every later analysis,
+// ordering and plan of that handle, gsx_update's included, takes them from there.  The defaults are what an empty
+// environment gives: the measured best.
+struct ScheduleOptions {
+  // GSX_TREE_TIERS ("rows:threads,...", e.g. "45:128,79:256,140:512"; "0": no tiers — the tree kernels off, level launches
+  // only): tier -> largest n of its fronts, workgroup size (0: the host's default for that n).
+  // two tiers: fronts of at most 67 rows (four to a CU's 160 KB of LDS) and the rest.  Swept on the 100 000-pose
+  // graphs (tools/sweep_tree.sh): every further tier adds its own tail — the last few chains of a launch run alone
+  // on the chip — and costs more than the LDS it frees: 45/79/140 +16 %, 53/98/140 +13 %, one tier +67 %.
+  std::vector<int> tree_bounds = {67, kSmallMaxN};
+  std::vector<int> tree_threads = {256, 512};
+  // GSX_MEDIUM set: fronts of 141-512 rows go to front_medium_body.
+  // MEASURED AND SWITCHED OFF (tests/test_gpu_parity.py keeps the path honest): a medium front
+  // takes ~53 us in its one workgroup (pose3_100k, mean n = 170, F = 45: children 13, panel 15, trailing update 18) and
+  // the medium fronts of a pose graph form a chain a dozen deep, while the level schedule of the blocked path gives up
+  // only six of its seventeen levels for them (the top fronts are wide in F): pose3_100k 2.94 -> 3.46 ms, pose2_100k
+  // 1.65 -> 1.99 ms with the medium tier on.
+  bool medium = false;
+  bool side = true;              // GSX_SIDE_OFF set: no second queue for the side leaves
+  // the side leaves are worth a second queue only when it moves real work: a tenth of the lean leaves, and thousands of them
+  // (GSX_SIDE_MIN lowers the count for experiments and for tests that reach the side group on a small graph)
+  int side_min = 4096;
+  int nd_leaf = 0;               // GSX_ND_LEAF: leaf size of the nested dissection; 0: the ordering kind's own (ordering.cpp)
+  // GSX_SMALL_THREADS_SHIFT: threads of the front_small launches as a shift of the row-per-thread count.
+  // (twice the threads the row-per-thread panel needed: the assembly and the stores of a front are a handful of memory
+  //  round trips that more lanes shorten, and the tile phases of the factorization split over the waves; measured -2 %
+  //  on the 100 000-pose graphs, nothing beyond 2x)
+  int small_threads_shift = 1;
+  bool h_tile = true;            // GSX_H_TILE_OFF set: H panels by the generic kernel, not assemble_h_tile_kernel (measurements)
+  bool fused_star = true;        // GSX_FUSED_STAR=0: star leaves by the two-step path (star assembly, then front_leaf)
+  bool star_leaf_pack = true;    // GSX_STAR_LEAF_PACK=0: every star leaf eliminated by a wave of its own
+  bool bs_leaf_pack = true;      // GSX_BS_LEAF_PACK=0: leaf back-substitution a wave per clique
+  bool bs_tree = true;           // GSX_BS_TREE_OFF set: back-substitution by level launches only, no tree launch
+  bool linerr_from_step = true;  // GSX_LINERR_DIRECT set: the LM trial's linearized error by direct evaluation
+};
+ScheduleOptions schedule_options_from_env();   // (schedule_options.cpp)
+
 struct HostProblem {
   int n_vars = 0, n_factors = 0;
   std::vector<uint64_t> keys;
@@ -218,7 +256,7 @@ gsx_status lower_problem(const gsx_problem_desc* d, HostProblem& P, std::string&
 // the directions of the packed states `values` are of unit length (to the 1e-9 of unit3_math.h); the first that is not is
 // named in err.  Nothing is normalised silently
 gsx_status check_direction_states(const HostProblem& P, const double* values, std::string& err);
-void compute_ordering(const HostProblem& P, int kind, std::vector<int>& order);
+void compute_ordering(const HostProblem& P, int kind, const ScheduleOptions& opt, std::vector<int>& order);
 // multilevel nested dissection of the vertices `verts` of the graph `adj` (nd.cpp); sets of at most `leaf` vertices and
 // the separators are ordered by `leaf_order` (appends to `out`)
 typedef void (*NdLeafOrder)(const std::vector<std::vector<int>>& adj, const std::vector<int>& w,
@@ -226,7 +264,7 @@ typedef void (*NdLeafOrder)(const std::vector<std::vector<int>>& adj, const std:
 void multilevel_nested_dissection(const std::vector<std::vector<int>>& adj, const std::vector<int>& w,
                                   const std::vector<int>& verts, int leaf, NdLeafOrder leaf_order, std::vector<int>& out);
 gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order, double relax, int relax_max_f,
-                             int shard_rank, int shard_world, Symbolic& S, std::string& err);
+                             int shard_rank, int shard_world, const ScheduleOptions& opt, Symbolic& S, std::string& err);
 
 // ---- Pose3 initialization (init_graph.cpp: host lowering; initialize.hip: device work) ----------------------------------
 // The pose graph of initialize::buildPoseGraph<Pose3> (gtsam/slam/InitializePose.h:36-52) over the POSE3 variables of a

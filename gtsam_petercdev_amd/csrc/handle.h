@@ -105,6 +105,7 @@ struct Context {
   bool has_device = false;
   hipStream_t stream = nullptr;
   HostProblem P;
+  ScheduleOptions opt;   // the schedule switches, read by gsx_create and kept for the handle's life
   Symbolic S;
   bool has_symbolic = false;
   double relax = GSX_AMALGAMATION_AUTO;  // relaxed amalgamation (gsx_set_amalgamation); 0 = the reference's cliques, < 0 = the library's choice
@@ -144,9 +145,8 @@ struct Context {
   int leaf_base = 0;             // schedule position of d_leaf_recs[0]
   // The back-substitution solves narrow leaf cliques several to a wave (kernels.hip: backsolve_leaf_packed): its own copy
   // of d_leaf_recs, partitioned into the 16-lane, 32-lane and wave classes with the order inside a class kept
-  // (leaf_bs_n: their sizes; all 0: no clique shares a wave and d_leaf_recs serves).  GSX_BS_LEAF_PACK=0 at gsx_create:
+  // (leaf_bs_n: their sizes; all 0: no clique shares a wave and d_leaf_recs serves).  ScheduleOptions::bs_leaf_pack off:
   // a wave per clique.
-  bool bs_leaf_pack_env = true;  // (read once per handle)
   DevBuf<LeafRec> d_leaf_bs_recs;
   int leaf_bs_n[3] = {0, 0, 0};
   int lin_err_slice = 0;         // LDS doubles per wave of the staged linear-error kernel (0: blocks too large, direct kernel)
@@ -174,7 +174,7 @@ struct Context {
   };
   std::vector<TreeTier> tree_tiers;
   // the back-substitution's launches (plan_backsolve).  bs_level_plan: every front level by level, top-down, over d_sched —
-  // the wildfire pass and GSX_BS_TREE_OFF.  bs_plan: the upper levels top-down over d_usched, the tree launch, the leaves.
+  // the wildfire pass and a handle with ScheduleOptions::bs_tree off.  bs_plan: the upper levels top-down over d_usched, the tree launch, the leaves.
   std::vector<BsLaunch> bs_level_plan, bs_plan;
   DevBuf<i64> d_gt_dst;  // gather tasks / segments for big parents
   DevBuf<GatherSeg> d_gsegs;
@@ -212,12 +212,10 @@ struct Context {
   int n_star_bundles = 0;
   // STAR LEAVES (kernels.hip: front_star_leaf_kernel): the star variables whose clique is a lean leaf are eliminated
   // straight from [A b] by the factorization, and their H panels are not assembled — only their rhs rows are written (by
-  // that kernel).  GSX_FUSED_STAR=0 at gsx_create: the two-step path (star assembly, then front_leaf).
-  bool fused_star_env = true;    // (read once per handle)
+  // that kernel).  ScheduleOptions::fused_star off: the two-step path (star assembly, then front_leaf).
   bool fused_star = false;       // this tree has star leaves and the handle eliminates them fused
   // Several star leaves share a wave (kernels.h: star_leaf_pack_class): the star records of a launch group are a stable
-  // partition into the cliques of 16 lanes, of 32 lanes and of a wave.  GSX_STAR_LEAF_PACK=0 at gsx_create: a wave each.
-  bool star_leaf_pack_env = true;   // (read once per handle)
+  // partition into the cliques of 16 lanes, of 32 lanes and of a wave.  ScheduleOptions::star_leaf_pack off: a wave each.
   struct LeafSplit {
     int sbegin, scount;          // the launch group's star leaves: range of d_star_recs
     int rbegin, rcount;          // its other leaves: range of d_leaf_rest_recs

@@ -524,7 +524,7 @@ static gsx_status gsx_update_impl(gsx_handle h, const gsx_problem_desc* desc, co
   const int relax_max_f = h->S.relax_max_f;
   const auto ta = std::chrono::steady_clock::now();
   Symbolic S2;
-  st = symbolic_analysis(P2, ord, relax, relax_max_f, 0, 1, S2, h->err);
+  st = symbolic_analysis(P2, ord, relax, relax_max_f, 0, 1, h->opt, S2, h->err);
   if (st != GSX_OK) return st;
   const double t_symbolic = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
   // switch the handle over (handle.h: problem_replaced — a failure from here on leaves every flag down)

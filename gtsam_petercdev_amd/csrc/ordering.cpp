@@ -110,13 +110,9 @@ static void min_degree(const Adj& adj, const std::vector<int>& w, const std::vec
   }
 }
 
-// (GSX_ND_LEAF overrides the leaf size of the dissection: a tuning knob of the stand-alone harness)
-static int nd_leaf(int dflt) {
-  const char* e = std::getenv("GSX_ND_LEAF");
-  return e ? std::max(1, std::atoi(e)) : dflt;
-}
-
-void compute_ordering(const HostProblem& P, int kind, std::vector<int>& order) {
+void compute_ordering(const HostProblem& P, int kind, const ScheduleOptions& opt, std::vector<int>& order) {
+  // (ScheduleOptions::nd_leaf overrides the leaf size of the dissection: a tuning knob of the stand-alone harness)
+  auto nd_leaf = [&](int dflt) { return opt.nd_leaf > 0 ? opt.nd_leaf : dflt; };
   order.clear();
   order.reserve(P.n_vars);
   if (kind == GSX_ORDER_NATURAL) {

@@ -408,8 +408,7 @@ static void dev_backsolve_levels(gsx_context* c, const WildfireArgs* wf) {
 // OptimizeClique top-down (gtsam/linear/linearAlgorithms-inst.h:49-117): the upper fronts level by level (Symbolic::ulevel),
 // then the tree fronts of all levels in one launch, then the leaf-kernel cliques.
 void dev_backsolve(gsx_context* c, const WildfireArgs* wf) {
-  static const bool levels_only = std::getenv("GSX_BS_TREE_OFF") != nullptr;
-  if (wf != nullptr || levels_only) {
+  if (wf != nullptr || !c->opt.bs_tree) {
     dev_backsolve_levels(c, wf);
     return;
   }
@@ -430,8 +429,7 @@ void dev_backsolve(gsx_context* c, const WildfireArgs* wf) {
 // otherwise (an arbitrary point: Dogleg, gsx_linear_error) the direct evaluation
 void dev_linear_error(gsx_context* c, bool solved_step) {
   // (hard constraints: the step solves the KKT system, not (H + lambda D) delta = g — the identity below does not hold)
-  static const bool direct_env = std::getenv("GSX_LINERR_DIRECT") != nullptr;
-  const bool direct_only = direct_env || c->constrained() || c->use_pcg();  // (PCG: the step is not exact either)
+  const bool direct_only = !c->opt.linerr_from_step || c->constrained() || c->use_pcg();  // (PCG: the step is not exact either)
   timer_begin(c, PH_LINERR);
   if (solved_step && !direct_only && c->h_ready) {
     if (!c->lin0_ready) {
@@ -664,14 +662,7 @@ gsx_status gsx_create(const gsx_problem_desc* desc, int32_t device, gsx_handle* 
   }
   c->n_smart = (int)std::count(c->P.f_type.begin(), c->P.f_type.end(), (int)GSX_F_SMART_PROJECTION);
   c->device = device;
-  {
-    const char* e = std::getenv("GSX_FUSED_STAR");
-    c->fused_star_env = !(e && std::atoi(e) == 0);
-    e = std::getenv("GSX_BS_LEAF_PACK");
-    c->bs_leaf_pack_env = !(e && std::atoi(e) == 0);
-    e = std::getenv("GSX_STAR_LEAF_PACK");
-    c->star_leaf_pack_env = !(e && std::atoi(e) == 0);
-  }
+  c->opt = schedule_options_from_env();
   int n = 0;
   if (hipGetDeviceCount(&n) == hipSuccess && n > 0 && device >= 0 && device < n && hipSetDevice(device) == hipSuccess &&
       hipStreamCreate(&c->stream) == hipSuccess) {
@@ -740,7 +731,7 @@ gsx_status gsx_set_ordering(gsx_handle h, const uint64_t* keys, int32_t n) {
     h->err = "a sharded handle takes no smart projection factors (their re-triangulation cache is per handle)";
     return GSX_E_STATE;
   }
-  gsx_status st = symbolic_analysis(h->P, ord, h->relax, h->relax_max_f, h->shard_rank, h->shard_world, h->S, h->err);
+  gsx_status st = symbolic_analysis(h->P, ord, h->relax, h->relax_max_f, h->shard_rank, h->shard_world, h->opt, h->S, h->err);
   if (st != GSX_OK) return st;
   h->order = ord;
   h->has_symbolic = true;
@@ -757,7 +748,7 @@ gsx_status gsx_set_ordering(gsx_handle h, const uint64_t* keys, int32_t n) {
 gsx_status gsx_compute_ordering(gsx_handle h, int32_t kind, uint64_t* keys_out) {
   if (!h || !keys_out || kind < 0 || kind > 4) return GSX_E_INVALID;
   std::vector<int> ord;
-  compute_ordering(h->P, kind, ord);
+  compute_ordering(h->P, kind, h->opt, ord);
   for (int i = 0; i < h->P.n_vars; ++i) keys_out[i] = h->P.keys[ord[i]];
   return GSX_OK;
 }

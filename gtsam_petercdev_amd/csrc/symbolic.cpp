@@ -34,7 +34,7 @@ struct PhaseClock {   // GSX_TIME_SYMBOLIC=1: phase times of the analysis on std
 }  // namespace
 
 gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order, double relax, int relax_max_f,
-                             int shard_rank, int shard_world, Symbolic& S, std::string& err) {
+                             int shard_rank, int shard_world, const ScheduleOptions& opt, Symbolic& S, std::string& err) {
   const int n = P.n_vars, m = P.n_factors;
   if ((int)order.size() != n) {
     err = "ordering size differs from the number of variables";
@@ -626,14 +626,9 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
   S.lean.assign(nfr, 0);
   S.cls.assign(nfr, 1);
   S.med.assign(nfr, 0);
-  // MEASURED AND SWITCHED OFF (GSX_MEDIUM=1 turns it on; tests/test_gpu_parity.py keeps the path honest): a medium front
-  // takes ~53 us in its one workgroup (pose3_100k, mean n = 170, F = 45: children 13, panel 15, trailing update 18) and
-  // the medium fronts of a pose graph form a chain a dozen deep, while the level schedule of the blocked path gives up
-  // only six of its seventeen levels for them (the top fronts are wide in F): pose3_100k 2.94 -> 3.46 ms, pose2_100k
-  // 1.65 -> 1.99 ms with the medium tier on.
-  const bool med_off = std::getenv("GSX_MEDIUM") == nullptr;
+  // (ScheduleOptions::medium: measured and switched off)
   for (int f = 0; f < nfr; ++f) {   // medium fronts first: a leaf's leanness depends on its parent's class
-    if (cap[f] || S.con[f] || S.N[f] <= kSmallMaxN || S.N[f] > kMedMaxN || (int64_t)S.N[f] * S.F[f] > kMedMaxPanel || med_off) continue;
+    if (cap[f] || S.con[f] || S.N[f] <= kSmallMaxN || S.N[f] > kMedMaxN || (int64_t)S.N[f] * S.F[f] > kMedMaxPanel || !opt.medium) continue;
     int leaf_kids = 0;
     for (int c = S.child_ptr[f]; c < S.child_ptr[f + 1]; ++c) {
       const int ch = S.children[c];
@@ -666,34 +661,8 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
   }
   // ---- tree fronts (gsx_internal.h): LDS-class fronts whose whole subtree is LDS-class, tiers by the subtree's largest n
   {
-    S.tree_bounds.clear();
-    S.tree_threads.clear();
-    if (const char* e = std::getenv("GSX_TREE_TIERS")) {  // experiments: "45:128,79:256,140:512"; "0" switches the tree kernels off
-      int v[2] = {0, 0}, k = 0;
-      bool any = false;
-      for (const char* q = e;; ++q) {
-        if (*q >= '0' && *q <= '9') {
-          v[k] = v[k] * 10 + (*q - '0');
-          any = true;
-        } else if (*q == ':') {
-          k = 1;
-        } else {
-          if (any && v[0] > 0) {
-            S.tree_bounds.push_back(std::min(v[0], kSmallMaxN));
-            S.tree_threads.push_back(std::max(0, std::min(512, (v[1] + 63) / 64 * 64)));   // (the kernel's launch bound)
-          }
-          v[0] = v[1] = k = 0;
-          any = false;
-          if (!*q) break;
-        }
-      }
-    } else {
-      // two tiers: fronts of at most 67 rows (four to a CU's 160 KB of LDS) and the rest.  Swept on the 100 000-pose
-      // graphs (tools/sweep_tree.sh): every further tier adds its own tail — the last few chains of a launch run alone
-      // on the chip — and costs more than the LDS it frees: 45/79/140 +16 %, 53/98/140 +13 %, one tier +67 %.
-      S.tree_bounds = {67, kSmallMaxN};
-      S.tree_threads = {256, 512};
-    }
+    S.tree_bounds = opt.tree_bounds;
+    S.tree_threads = opt.tree_threads;
     // one start-list cursor per tier, the medium tier included: the bounds past kMaxTreeTiers - 1 are dropped, and fronts
     // taller than the last bound kept are no tree fronts — they go to the upper schedule (below)
     if ((int)S.tree_bounds.size() > kMaxTreeTiers - 1) {
@@ -983,12 +952,11 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
   S.side.assign(nfr, 0);
   S.side_level0 = -1;
   {
-    static const bool side_off = std::getenv("GSX_SIDE_OFF") != nullptr;
     int l0 = -1;
     for (int f = 0; f < nfr; ++f)
       if (S.cls[f] == 2 && S.scheduled[f] && (l0 < 0 || S.ulevel[f] < l0)) l0 = S.ulevel[f];
     int64_t n_side = 0, n_lean = 0;
-    if (l0 >= 0 && !side_off && S.shard_world == 1)
+    if (l0 >= 0 && opt.side && S.shard_world == 1)
       for (int f = 0; f < nfr; ++f)
         if (S.lean[f] && S.scheduled[f]) {
           ++n_lean;
@@ -997,11 +965,8 @@ gsx_status symbolic_analysis(const HostProblem& P, const std::vector<int>& order
             ++n_side;
           }
         }
-    // (worth a second queue only when it moves real work: a tenth of the lean leaves, and thousands of them)
-    // (GSX_SIDE_MIN lowers the count for experiments and for tests that reach the side group on a small graph)
-    int64_t side_min = 4096;
-    if (const char* e = std::getenv("GSX_SIDE_MIN")) side_min = std::max(1, std::atoi(e));
-    if (n_side >= side_min && n_side * 10 >= n_lean) S.side_level0 = l0;
+    // (worth a second queue only when it moves real work: a tenth of the lean leaves, and ScheduleOptions::side_min of them)
+    if (n_side >= opt.side_min && n_side * 10 >= n_lean) S.side_level0 = l0;
     else std::fill(S.side.begin(), S.side.end(), 0);
   }
   // ---- schedule: by level; inside a level: leaf-kernel fronts, other small (LDS) fronts by N, big fronts ----

@@ -242,16 +242,13 @@ gsx_status upload_problem(gsx_context* c) {
   return GSX_OK;
 }
 
-static int small_threads_for(int n) {
-  // (twice the threads the row-per-thread panel needed: the assembly and the stores of a front are a handful of memory
-  //  round trips that more lanes shorten, and the tile phases of the factorization split over the waves; measured -2 %
-  //  on the 100 000-pose graphs, nothing beyond 2x; GSX_SMALL_THREADS_SHIFT overrides for experiments)
-  static const int shift = std::getenv("GSX_SMALL_THREADS_SHIFT") ? std::atoi(std::getenv("GSX_SMALL_THREADS_SHIFT")) : 1;
+// (ScheduleOptions::small_threads_shift: twice the threads the row-per-thread panel needed)
+static int small_threads_for(const gsx_context* c, int n) {
   int t = 512;
   if (n <= 48) t = 64;
   else if (n <= 72) t = 128;
   else if (n <= 100) t = 256;
-  return std::min(512, t << shift);
+  return std::min(512, t << c->opt.small_threads_shift);
 }
 
 // ---- the back-substitution's launch plan (handle.h: BsLaunch) -----------------------------------------------------------
@@ -332,7 +329,7 @@ extern "C" int gsxtest_backsolve_plan(gsx_context* c, int which, int* out, int c
     if (which == 1) recs.push_back({b.kind, b.level, b.count, b.threads, b.max_n});
   for (size_t i = 0; which == 0 && i < level_plan.size(); ++i) {
     const BsLaunch& b = level_plan[i];
-    const bool packs = b.kind == BS_LEAF && b.level == 0 && c->bs_leaf_pack_env;
+    const bool packs = b.kind == BS_LEAF && b.level == 0 && c->opt.bs_leaf_pack;
     int leaf_max_F = 0;
     for (int k = b.begin; packs && k < b.begin + b.count; ++k) leaf_max_F = std::max(leaf_max_F, S.F[S.sched[k]]);
     for (int k = b.begin; k < b.begin + b.count; ++k) {
@@ -396,11 +393,10 @@ void plan_hessian_groups(gsx_context* c) {
   };
   std::vector<VI> light, heavy, huge, diag, star, tile;
   // a "tile" variable: at most 64 terms, all from NARROW factors (<= 16 columns with the rhs, <= 8 rows): one matrix-core
-  // product per factor (assemble_h_tile_kernel).  GSX_H_TILE_OFF keeps the generic kernel (measurements).
-  static const bool tile_off = std::getenv("GSX_H_TILE_OFF") != nullptr;
+  // product per factor (assemble_h_tile_kernel).  ScheduleOptions::h_tile off keeps the generic kernel (measurements).
   auto is_tile = [&](int v) {
     const int64_t tb = S.term_ptr[v], te = S.term_ptr[v + 1];
-    if (tile_off || te - tb < 2 || te - tb > 64 || (int64_t)S.h_rows[v] * P.dims[v] * 8 * 4 > 48 * 1024) return false;
+    if (!c->opt.h_tile || te - tb < 2 || te - tb > 64 || (int64_t)S.h_rows[v] * P.dims[v] * 8 * 4 > 48 * 1024) return false;
     int64_t t = tb;
     while (t < te) {
       int64_t e = t + 1;
@@ -618,7 +614,7 @@ gsx_status upload_symbolic(gsx_context* c) {
     int max_F = 0, cnt[3] = {0, 0, 0};
     auto cls = [&](const LeafRec& r) { const int g = leaf_pack_class(r.n, r.F, max_F); return g == 16 ? 0 : g == 32 ? 1 : 2; };
     for (const LeafRec& r : lr) max_F = std::max(max_F, r.F);
-    if (c->bs_leaf_pack_env)
+    if (c->opt.bs_leaf_pack)
       for (const LeafRec& r : lr) ++cnt[cls(r)];
     c->leaf_bs_n[0] = c->leaf_bs_n[1] = c->leaf_bs_n[2] = 0;
     if (cnt[0] + cnt[1] > 0) {
@@ -679,12 +675,12 @@ gsx_status upload_symbolic(gsx_context* c) {
     int se_lds = se;   // the medium fronts (n > kSmallMaxN) sit at the end of the level's LDS-class range (sorted by n)
     while (se_lds > i && S.med[S.sched[se_lds - 1]]) --se_lds;
     while (i < se_lds) {
-      const int thr = small_threads_for(S.N[S.sched[i]]);
+      const int thr = small_threads_for(c, S.N[S.sched[i]]);
       int j = i, maxn = 0;
       // same thread class, and rows within 1.6x of the smallest member (LDS footprint within 2.6x: in effect one group per
       // thread class — measured on the 100 000-pose graphs: 4 launches per level beat 7 finer ones (1.3x) by 3 %)
       const int n0 = std::max(S.N[S.sched[i]], 12);
-      while (j < se_lds && small_threads_for(S.N[S.sched[j]]) == thr && S.N[S.sched[j]] * 10 <= n0 * 16) {
+      while (j < se_lds && small_threads_for(c, S.N[S.sched[j]]) == thr && S.N[S.sched[j]] * 10 <= n0 * 16) {
         maxn = std::max(maxn, S.N[S.sched[j]]);
         ++j;
       }
@@ -724,7 +720,7 @@ gsx_status upload_symbolic(gsx_context* c) {
         maxn = std::max(maxn, g.max_n);
       }
       if (G.size() > 1 && total <= 256) {
-        const SmallLaunch one{G[0].begin, total, maxn, std::max(256, small_threads_for(maxn))};
+        const SmallLaunch one{G[0].begin, total, maxn, std::max(256, small_threads_for(c, maxn))};
         G.assign(1, one);
       }
       if (se_lds < se) {   // the level's medium fronts: one group
@@ -757,7 +753,7 @@ gsx_status upload_symbolic(gsx_context* c) {
         r.max_F = std::max(r.max_F, S.F[f]);
         r.max_panel = std::max(r.max_panel, S.N[f] * S.F[f]);
       }
-      r.threads = r.medium ? 512 : small_threads_for(r.max_n);
+      r.threads = r.medium ? 512 : small_threads_for(c, r.max_n);
       if (r.count) c->rest_launch[l].push_back(r);
     }
     BigLevel& B = c->big_level[l];
@@ -852,7 +848,7 @@ gsx_status upload_symbolic(gsx_context* c) {
           lds = std::max(lds, S.med[f] ? (size_t)S.N[f] * S.F[f] + S.N[f] : (size_t)S.N[f] * S.N[f] + S.N[f]);
         }
       c->tree_tiers.push_back({S.tree_start_ptr[t], S.tree_start_ptr[t + 1] - S.tree_start_ptr[t], maxn,
-                               t < nb ? (S.tree_threads[t] > 0 ? S.tree_threads[t] : small_threads_for(maxn)) : 512,
+                               t < nb ? (S.tree_threads[t] > 0 ? S.tree_threads[t] : small_threads_for(c, maxn)) : 512,
                                t >= nb ? lds * sizeof(double) : (size_t)0});
     }
     HIPCHK(c, c->d_tree_start.upload(S.tree_start, st));
@@ -959,7 +955,7 @@ gsx_status upload_symbolic(gsx_context* c) {
     int sgrp = -1;
     for (size_t g = 0; g < c->hgroups.size(); ++g)
       if (c->hgroups[g].threads == -1) sgrp = (int)g;
-    if (c->fused_star_env && sgrp >= 0 && !c->sharded() && !c->constrained() && S.n_levels > 0) {
+    if (c->opt.fused_star && sgrp >= 0 && !c->sharded() && !c->constrained() && S.n_levels > 0) {
       auto star_leaf = [&](const LeafRec& r) {
         const int v = S.fvars[S.fvar_ptr[r.front]];
         if (c->hv_group_of_var[v] != sgrp || r.nfv != 1 || !r.lean || r.F != r.dA || r.dA > kStarMaxD || r.loc != 0 ||
@@ -1006,7 +1002,7 @@ gsx_status upload_symbolic(gsx_context* c) {
                                      hm[r.n - 1], 0});
         }
         ls.scount = (int)srec.size() - ls.sbegin;
-        partition_star_leaves(srec.data() + ls.sbegin, ls.scount, c->star_leaf_pack_env, ls.s16, ls.s32);
+        partition_star_leaves(srec.data() + ls.sbegin, ls.scount, c->opt.star_leaf_pack, ls.s16, ls.s32);
         ls.rcount = (int)rrec.size() - ls.rbegin;
         c->leaf_split.push_back(ls);
       }

@@ -584,8 +584,9 @@ gsx_status gsx_get_gather_plan(gsx_handle h, int32_t* n_segments, int64_t* n_sou
  *                   shape, and how many variables the bundle holds; -1 and 0 when the star group runs unbundled (one
  *                   variable has more than 64 factors) and for every other class
  *   *fused_diag_star   1 when the star bundles and the diag group run in one launch.  A handle that eliminates star
- *                   leaves straight from [A b] (the default when the tree has some; not GSX_FUSED_STAR=0, not a handle
- *                   without a device) launches the two apart: 0. */
+ *                   leaves straight from [A b] (the default when the tree has some; not a handle created under
+ *                   GSX_FUSED_STAR=0 — like every schedule switch it is read by gsx_create and kept for the handle's
+ *                   life — and not a handle without a device) launches the two apart: 0. */
 enum { GSX_H_TILE = 0, GSX_H_LIGHT = 1, GSX_H_HEAVY = 2, GSX_H_HUGE = 3, GSX_H_STAR = 4, GSX_H_DIAG = 5 };
 gsx_status gsx_get_hessian_groups(gsx_handle h, int32_t* classes, int32_t* group, int32_t* position, int32_t* bundle,
                                   int32_t* bundle_size, int32_t* fused_diag_star);

@@ -213,7 +213,7 @@ def tree_shape(arr, ordering, amalgamation=DEEP_AMALGAMATION):
             "tree_classes": set(cls[f] for f in range(nf) if tree[f]), "n_big_fronts": int(st["n_big_fronts"])}
 
 
-# name -> (maker, environment of the symbolic analysis, amalgamation)
+# name -> (maker, environment the handle is created under, amalgamation)
 DEEP_DENSE = {
     "chain600": (lambda: chain(600, 3), {}, DEEP_AMALGAMATION),
     "broom65": (lambda: broom(65, 3, 6), {}, DEEP_AMALGAMATION),

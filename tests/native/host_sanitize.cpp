@@ -23,15 +23,16 @@ static int check(const char* what, gsx_dataset* ds, const std::string& tmp) {
     std::fprintf(stderr, "%s: lower_problem: %s\n", what, err.c_str());
     return 1;
   }
+  const gsx::ScheduleOptions opt{};   // the defaults: what a handle gets under an empty environment
   for (int kind = 0; kind <= 4; ++kind) {
     std::vector<int> order;
-    gsx::compute_ordering(P, kind, order);
+    gsx::compute_ordering(P, kind, opt, order);
     if ((int)order.size() != P.n_vars) return 1;
     for (double relax : {0.0, 0.5})
       for (int world : {1, 2, 3, 8})
         for (int rank = 0; rank < world; rank += (world > 2 ? world - 1 : 1)) {
           gsx::Symbolic S;
-          if (gsx::symbolic_analysis(P, order, relax, 64, rank, world, S, err) != GSX_OK) {
+          if (gsx::symbolic_analysis(P, order, relax, 64, rank, world, opt, S, err) != GSX_OK) {
             std::fprintf(stderr, "%s: symbolic (kind %d, relax %g, %d/%d): %s\n", what, kind, relax, rank, world, err.c_str());
             return 1;
           }

@@ -17,14 +17,13 @@ unbundled launch over the star variables that are no leaves wrote; that those ro
 through the partial path (unbundled against bundled) and, for the star leaves, by test_gpu_fused_star.py through the
 solves.
 """
-import os
-
 import numpy as np
 import pytest
 
 from gtsam_petercdev_amd import _abi as A
 
 from tests import _assembly_cases as AC
+from tests._switches import switches
 
 pytestmark = pytest.mark.gpu
 
@@ -41,15 +40,8 @@ def gpu():
 
 def _two_step(gpu, arr):
     """A handle that keeps the two-step star path (the switch is read when a handle is created)."""
-    old = os.environ.get("GSX_FUSED_STAR")
-    os.environ["GSX_FUSED_STAR"] = "0"
-    try:
+    with switches(GSX_FUSED_STAR="0"):
         return gpu.product_backend(arr)
-    finally:
-        if old is None:
-            del os.environ["GSX_FUSED_STAR"]
-        else:
-            os.environ["GSX_FUSED_STAR"] = old
 
 
 def _panels(be, arr):

@@ -17,7 +17,6 @@ The packed results are also held to the float64 backward-error bounds of tests/t
 its neighbouring-lambda sequence on one handle), and a wildfire pass in which whole cliques are skipped inside shared
 waves must leave the same words as the wave-per-clique handle's.
 """
-import os
 from collections import Counter
 
 import numpy as np
@@ -25,6 +24,7 @@ import pytest
 
 from gtsam_petercdev_amd import _abi as A
 from gtsam_petercdev_amd import datasets
+from tests._switches import switches
 from tests.test_gpu_linear_bounds import _device_case, _judge
 
 pytestmark = pytest.mark.gpu
@@ -74,15 +74,8 @@ def _arrays(name):
 def _pair(gpu, arr, kind, amalgamation):
     """(packed handle, wave-per-clique handle) under one ordering (the switch is read when a handle is created)."""
     packed = gpu.product_backend(arr)
-    old = os.environ.get("GSX_BS_LEAF_PACK")
-    os.environ["GSX_BS_LEAF_PACK"] = "0"
-    try:
+    with switches(GSX_BS_LEAF_PACK="0"):
         plain = gpu.product_backend(arr)
-    finally:
-        if old is None:
-            del os.environ["GSX_BS_LEAF_PACK"]
-        else:
-            os.environ["GSX_BS_LEAF_PACK"] = old
     ordering = packed.compute_ordering(kind)
     for be in (packed, plain):
         be.set_amalgamation(*amalgamation)

@@ -6,13 +6,13 @@ tolerance: solves at lambda I and with diagonal damping, the linearized errors, 
 conditionals of landmark cliques, diag(H) and Dogleg after a fused step, robust noise, a landmark seen by more than 64
 cameras, a repeated camera-landmark pair, and the failures a cheirality or an indefinite landmark produces.
 """
-import os
-
 import numpy as np
 import pytest
 
 from gtsam_petercdev_amd import _abi as A
 from gtsam_petercdev_amd import datasets
+
+from ._switches import switches
 
 pytestmark = pytest.mark.gpu
 
@@ -27,15 +27,8 @@ def gpu():
 def _handles(gpu, arr, ordering=None):
     """(fused handle, two-step handle) with the same ordering (the switch is read when a handle is created)."""
     fused = gpu.product_backend(arr)
-    old = os.environ.get("GSX_FUSED_STAR")
-    os.environ["GSX_FUSED_STAR"] = "0"
-    try:
+    with switches(GSX_FUSED_STAR="0"):
         two = gpu.product_backend(arr)
-    finally:
-        if old is None:
-            del os.environ["GSX_FUSED_STAR"]
-        else:
-            os.environ["GSX_FUSED_STAR"] = old
     if ordering is None:
         ordering = fused.compute_ordering(A.ORDER_SCHUR)
     fused.set_ordering(ordering)

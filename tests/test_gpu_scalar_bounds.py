@@ -24,9 +24,9 @@ Which kernel a case reaches (kernels.hip):
 No public observable tells the staged from the direct kernel (gsx_kernel_time's "linear_error" phase covers both), so the
 cases rely on the rule that decides: upload.hip: upload_problem sets lin_err_slice from the largest [A b] range of 64 consecutive
 factors (0 above 96 KB for the two waves), kernels.hip:1002 takes the staged kernel iff it is positive.
-_scalar_cases.slice_of restates the rule and every case asserts the side it is on.  GSX_LINERR_DIRECT is read once per
-process into a static (solver.hip: dev_linear_error), so the direct evaluation next to the model path is taken through
-gsx_linear_error, which never uses the model.
+_scalar_cases.slice_of restates the rule and every case asserts the side it is on.  Here the direct evaluation next to the model path
+is taken through gsx_linear_error, which never uses the model; a handle created under GSX_LINERR_DIRECT (read when the
+handle is created, like every schedule switch) is judged beside a default one in tests/test_gpu_schedule_options.py.
 
 Dogleg on a linear graph: a GSX_F_LINEAR factor has no nonlinear error (kernels.hip:662 returns 0), so the loop is entered
 with error_tol = -1, f(0) - f(dx) = 0 makes rho 0.5 by the 1e-15 guard (optimizers.hip: gsx_dogleg_optimize), the first trial is accepted with

@@ -10,7 +10,6 @@ lanes_of (test_host_star_leaf_partition.py) restates the rule, and the library's
 (gsxtest_star_leaf_classes) are held to it.  Landmark 0 carries the prior of bal_arrays: it is no star variable.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ import pytest
 from gtsam_petercdev_amd import _abi as A
 from gtsam_petercdev_amd import datasets
 
+from ._switches import switches
 from .test_gpu_fused_star import _huber, _landmark_cliques, _sfm_pairs
 from .test_host_star_leaf_partition import lanes_of
 
@@ -83,17 +83,8 @@ def _arrays(name, **kw):
 def _under(gpu, arr, var, ordering, reference_tree=False):
     """A handle made with `var` set to 0 (None: a default handle) under the ordering; reference_tree: without the relaxed
     amalgamation, which on a bundle of a few landmarks folds some of them into the cliques of their cameras."""
-    old = os.environ.get(var) if var else None
-    if var:
-        os.environ[var] = "0"
-    try:
+    with switches(**({var: "0"} if var else {})):
         be = gpu.product_backend(arr)
-    finally:
-        if var:
-            if old is None:
-                del os.environ[var]
-            else:
-                os.environ[var] = old
     if reference_tree:
         be.set_amalgamation(0.0, 128)
     be.set_ordering(ordering)

@@ -35,13 +35,12 @@ generic256 2.86 (146), generic1024 3.54 (1196), combined1024 2.96 (432), big 3.1
 factorization: factor at most 8.8 u, rhs at most 3.6 u against k of 800 to 1900.  Every count was exact and every
 untouched clique bit-equal; the whole module takes under five seconds.
 """
-import os
-
 import numpy as np
 import pytest
 
 from tests import _ld_linear as J
 from tests import _wildfire_cases as W
+from tests._switches import switches
 
 pytestmark = pytest.mark.gpu
 
@@ -69,17 +68,8 @@ def big_lds(gpu):
 
 def _handle(gpu, case, amalgamation, packed=True):
     """A handle under the case's ordering; packed=False: made under GSX_BS_LEAF_PACK=0 (read when a handle is created)."""
-    old = os.environ.get("GSX_BS_LEAF_PACK")
-    if not packed:
-        os.environ["GSX_BS_LEAF_PACK"] = "0"
-    try:
+    with switches(**({} if packed else {"GSX_BS_LEAF_PACK": "0"})):
         gb = gpu.product_backend(case.arr)
-    finally:
-        if not packed:
-            if old is None:
-                del os.environ["GSX_BS_LEAF_PACK"]
-            else:
-                os.environ["GSX_BS_LEAF_PACK"] = old
     gb.set_amalgamation(*amalgamation)
     gb.set_ordering(case.arr.var_keys[case.ordering])
     return gb

@@ -12,13 +12,13 @@ The default plan — the upper levels top-down, the one tree launch, the leaves 
 tests/_linear_cases.py (no upper front at all) and on a wildfire case with blocked fronts, tree fronts and leaves."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
 
 from tests import _linear_cases as L
 from tests import _wildfire_cases as W
+from tests._switches import switches
 
 BIG, SMALL, GENERIC, LEAF, TREE = range(5)       # handle.h: BsKind
 AMALGAMATIONS = {"reference": W.AMALGAMATION, "relaxed": W.RELAXED}
@@ -37,17 +37,8 @@ def _plans(arr, ordering, amalgamation, packed=True):
     level, count, threads, max_n)) of a host-only handle; packed=False: made under GSX_BS_LEAF_PACK=0 (read when a handle
     is created)."""
     from gtsam_petercdev_amd import _lib
-    old = os.environ.get("GSX_BS_LEAF_PACK")
-    if packed:
-        os.environ.pop("GSX_BS_LEAF_PACK", None)
-    else:
-        os.environ["GSX_BS_LEAF_PACK"] = "0"
-    try:
+    with switches(GSX_BS_LEAF_PACK=None if packed else "0"):
         hb = _lib.ProductBackend(arr, host_only=True)
-    finally:
-        os.environ.pop("GSX_BS_LEAF_PACK", None)
-        if old is not None:
-            os.environ["GSX_BS_LEAF_PACK"] = old
     hb.set_amalgamation(*amalgamation)
     hb.set_ordering(ordering)
     parent, fronts = hb.get_tree()
